@@ -33,7 +33,7 @@ if [ "${TESTS:-1}" = 1 ]; then
 fi
 if [ "${BENCH:-1}" = 1 ]; then
   for c in ${CONFIGS:-c2 c1 c2s c2x c3 c4 c5 t2j-c2 t2j-c3 agg}; do
-    timeout -k 10 900 python -u bench.py --config $c > $O/${c}_bench.json 2> $O/${c}_bench.err || { tail -20 $O/${c}_bench.err; exit 1; }
+    timeout -k 10 900 python -u bench.py --config $c --full > $O/${c}_bench.json 2> $O/${c}_bench.err || { tail -20 $O/${c}_bench.err; exit 1; }
     python -c "$J" $O/${c}_bench.json
   done
 fi
@@ -41,7 +41,7 @@ cd /tmp && export TMPDIR=/tmp
 if [ "${KSTATS:-1}" = 1 ]; then
   for c in ${KCONFIGS:-c2 c3 c4 c5 t2j-c2 t2j-c3}; do
     [ $c = c5 ] && c5_cache
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/kt_$c -o run -- python3 -u $ROOT/bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-e2e --inflight 1 > $ROOT/$O/kt_$c.log 2>&1 || { tail -20 $ROOT/$O/kt_$c.log; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$O/kt_$c -o run -- python3 -u $ROOT/bench.py --config $c --steps 5 --warmup 1 --full --no-cpu-baseline --no-e2e --inflight 1 > $ROOT/$O/kt_$c.log 2>&1 || { tail -20 $ROOT/$O/kt_$c.log; exit 1; }
     [ $c = c5 ] && c5_release
   done
   find $ROOT/$O -name "*kernel_stats.csv"
@@ -52,7 +52,7 @@ if [ "${TRAFFIC:-1}" = 1 ]; then
     i=0
     for P in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_RDREQ_32B TCC_EA0_RDREQ_64B TCC_EA0_RDREQ_128B"; do
       i=$((i+1))
-      timeout -s KILL 120 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $ROOT/$O/tr_${c}_$i -o run -- python3 -u $ROOT/bench.py --config $c --steps ${TR_STEPS:-2} --warmup 1 --no-cpu-baseline --no-e2e --inflight 1 > $ROOT/$O/tr_${c}_$i.log 2>&1 || { tail -20 $ROOT/$O/tr_${c}_$i.log; exit 1; }
+      timeout -s KILL 120 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $ROOT/$O/tr_${c}_$i -o run -- python3 -u $ROOT/bench.py --config $c --steps ${TR_STEPS:-2} --warmup 1 --full --no-cpu-baseline --no-e2e --inflight 1 > $ROOT/$O/tr_${c}_$i.log 2>&1 || { tail -20 $ROOT/$O/tr_${c}_$i.log; exit 1; }
     done
     python3 $ROOT/tools/traffic.py $ROOT/$O/tr_${c}_1/run_counter_collection.csv $ROOT/$O/tr_${c}_2/run_counter_collection.csv $(kern $c) $ROOT/$O/traffic_$c.json $ROOT/$O/tr_${c}_3/run_counter_collection.csv > /dev/null || exit 1
     python3 -c 'import json,sys;d=json.load(open(sys.argv[1]));print(sys.argv[2],d["hbm_bytes_per_launch"],d.get("hbm_bytes_per_launch_by_request_size"))' $ROOT/$O/traffic_$c.json $c
@@ -68,7 +68,7 @@ if [ "${SQ:-0}" = 1 ]; then
         lds) PMC="SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_LDS_UNALIGNED_STALL SQ_BUSY_CYCLES" ;;
         vmem) PMC="SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM_WR SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_WR_TA_DATA_FIFO_FULL SQ_INST_LEVEL_VMEM SQ_WAVE_CYCLES" ;;
       esac
-      timeout -s KILL 90 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $ROOT/$O/sq_${pass}_$c -o run -- python3 -u $ROOT/bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --inflight 1 > $ROOT/$O/sq_${pass}_$c.log 2>&1 || { tail -20 $ROOT/$O/sq_${pass}_$c.log; exit 1; }
+      timeout -s KILL 90 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $ROOT/$O/sq_${pass}_$c -o run -- python3 -u $ROOT/bench.py --config $c --steps 2 --warmup 1 --full --no-cpu-baseline --no-e2e --inflight 1 > $ROOT/$O/sq_${pass}_$c.log 2>&1 || { tail -20 $ROOT/$O/sq_${pass}_$c.log; exit 1; }
     done
   done
 fi
