@@ -21,7 +21,8 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_agg_submit", "dg_agg_wait", "dg_agg_ready", "dg_agg_stats", "dg_agg_profile", "dg_agg_destroy", "dg_agg_drive", "dg_agg_wait_gen", "dg_agg_ticket_gen", "dg_agg_set_knob",
            "dg_agg_gateway_drive", "dg_j2t_pipeline_host", "dg_bench_device", "dg_desc_attach_t2j", "dg_t2j_slot_bound", "dg_t2j_batch_device", "dg_t2j_batch_device_ml",
            "dg_t2j_batch_host", "dg_t2j_batch_device_aux", "dg_t2j_batch_host_aux",
-           "dg_t2j_batch_device_cb", "dg_t2j_batch_host_cb"]
+           "dg_t2j_batch_device_cb", "dg_t2j_batch_host_cb",
+           "dg_path_create", "dg_path_destroy", "dg_path_count", "dg_tget_batch_device", "dg_tget_batch_host"]
 
 _lib = None
 
@@ -102,6 +103,11 @@ def lib() -> C.CDLL:
         "dg_t2j_batch_device_cb": (i32, [vp, vp, u32, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, u64]),
         "dg_t2j_batch_host_cb": (i32, [vp, vp, u32, vp, vp, u64, u64, vp, u64, vp, vp, P64, vp, vp]),
         "dg_bench_device": (i32, [vp, vp, u32, vp, vp, u64, u64, vp, vp, vp, vp, i32, C.POINTER(C.c_float)]),
+        "dg_path_create": (i32, [vp, C.c_char_p, sz, C.POINTER(vp)]),
+        "dg_path_destroy": (None, [vp]),
+        "dg_path_count": (u32, [vp]),
+        "dg_tget_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, u64]),
+        "dg_tget_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -90,6 +90,7 @@ struct Knobs {
     int64_t t2j_overlap = 0;    /* t2j: 1 = the wave kernel on a second stream beside the lane pass; r4n t2j-c3: 65.1 GB/s with, 66.6 without (the lane pass is ~15 us of 1.21 ms, the route kernel adds 14) */
     int64_t t2j_wave_min = 256; /* t2j messages longer than this take the wave kernel (0: never); r4k t2j-c3: 128 / 192 / 256 / 384 / 512 / 1024 -> 66.1 / 66.5 / 66.3 / 59.4 / 53.7 / 23.3 GB/s */
     int64_t flat_wrap = -1;     /* the flat kernel's wrapped mode for roots that wrap a flat struct (0: off) */
+    int64_t tget_spread = 0;    /* tget: lanes per (message, path) pair, 0 = from the longest message (tget_host.hip) */
 };
 
 struct dg_ctx {
@@ -126,6 +127,15 @@ struct dg_ctx {
     uint8_t *ws_t2w = nullptr;
     hipEvent_t ws_t2w_done = nullptr;
     hipStream_t ws_t2w_last = nullptr;
+    /* tget (tget_host.hip): the deep pass's frames (32 MB, allocated by the
+     * first lookup), its queue and the two alternating queue counters, one per
+     * context, ordered across streams by tget_done recorded on tget_last */
+    uint8_t *ws_tget = nullptr;
+    uint32_t *tget_cnt = nullptr;
+    uint32_t *tget_list = nullptr; uint64_t tget_list_cap = 0;
+    uint32_t tget_set = 0;
+    hipEvent_t tget_done = nullptr;
+    hipStream_t tget_last = nullptr;
     /* dg_j2t_pipeline_host: its per-chunk buffers (j2t_pipe.hip PipeBuf),
      * kept across calls; pipe_mu serialises pipeline calls */
     std::mutex pipe_mu;

@@ -119,6 +119,7 @@ void dg_i_scratch_release(dg_ctx *c, const hipStream_t *s, int n)
     for (int k = 0; k < n; k++) { /* the t2j workspaces' last streams */
         if (c->ws_t2j_last == s[k]) c->ws_t2j_last = nullptr;
         if (c->ws_t2w_last == s[k]) c->ws_t2w_last = nullptr;
+        if (c->tget_last == s[k]) c->tget_last = nullptr;
     }
 }
 
@@ -162,6 +163,7 @@ static int64_t *knob_ref(dg_ctx *c, const char *name)
     if (!strcmp(name, "t2j_wave_min")) return &K.t2j_wave_min;
     if (!strcmp(name, "t2j_overlap")) return &K.t2j_overlap;
     if (!strcmp(name, "flat_wrap")) return &K.flat_wrap;
+    if (!strcmp(name, "tget_spread")) return &K.tget_spread;
     return nullptr;
 }
 
@@ -195,7 +197,8 @@ int dg_ctx_create(int device, dg_ctx **out)
     static const struct { const char *env; const char *name; } envk[] = {
         {"DG_FLAT", "flat"}, {"DG_WAVE_MIN", "wave_min"}, {"DG_WAVE_OCC", "wave_occ"},
         {"DG_SMALL_MPW", "small_mpw"}, {"DG_LIST_BLOCKS", "list_blocks"}, {"DG_T2J_SPREAD", "t2j_spread"},
-        {"DG_T2J_WAVE_MIN", "t2j_wave_min"}, {"DG_T2J_OVERLAP", "t2j_overlap"}, {"DG_FLAT_WRAP", "flat_wrap"}};
+        {"DG_T2J_WAVE_MIN", "t2j_wave_min"}, {"DG_T2J_OVERLAP", "t2j_overlap"}, {"DG_FLAT_WRAP", "flat_wrap"},
+        {"DG_TGET_SPREAD", "tget_spread"}};
     for (const auto &e : envk) {
         const char *v = getenv(e.env);
         if (v && *v) *knob_ref(c, e.name) = strtoll(v, nullptr, 10);
@@ -251,6 +254,10 @@ void dg_ctx_destroy(dg_ctx *c)
     if (c->ws_t2j_done) (void)hipEventDestroy(c->ws_t2j_done);
     (void)hipFree(c->ws_t2w);
     if (c->ws_t2w_done) (void)hipEventDestroy(c->ws_t2w_done);
+    (void)hipFree(c->ws_tget);
+    (void)hipFree(c->tget_cnt);
+    (void)hipFree(c->tget_list);
+    if (c->tget_done) (void)hipEventDestroy(c->tget_done);
     for (hipStream_t x : c->side) (void)hipStreamDestroy(x);
     for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);

@@ -1,0 +1,210 @@
+/*
+ * tget_host.hip — the C ABI of the batched path lookup (include/dgj2t.h
+ * dg_path_* / dg_tget_*; the reference's thrift/generic GetByPath). Kernels:
+ * tget_device.h.
+ */
+#include <string.h>
+
+#include "host_internal.h"
+#include "tget_device.h"
+
+using namespace dg;
+
+struct dg_path {
+    dg_ctx *ctx;
+    uint8_t *d_blob;
+    dg_path_hdr hdr;
+};
+
+static const uint64_t TGET_WS = (uint64_t)TG_DEEP_DEPTH * TG_DEEP_LANES * 8;
+
+/* every how-manieth lane takes a (message, path) pair. The t2j lane pass
+ * spreads ~1 KB messages over sparse waves (t2j_host.hip t2j_spread); the
+ * lookup, which formats nothing, measured fastest with dense waves at both
+ * batch sizes (ms per launch at spread 1 / 2 / 4: t2j-c3, ~1.2 KB, 4 paths
+ * 0.150 / 0.226 / 0.356, 1 path 0.101 / 0.100 / 0.106; t2j-c2, ~100 B, 4 paths
+ * 0.061 / 0.066 / 0.076), so max_len picks 1 at every length today and stays
+ * the handle for a length where that stops holding. The tget_spread knob
+ * (1|2|4) forces. */
+static uint32_t tget_spread(const dg_ctx *c, uint64_t max_len)
+{
+    const int64_t v = c->knobs.tget_spread;
+    if (v) return v == 1 || v == 4 ? (uint32_t)v : 2u;
+    (void)max_len;
+    return 1;
+}
+
+/* one batch on stream s (ctx mutex held). The deep queue, its two counters
+ * and the deep frames are one per context: a launch on another stream than
+ * the previous one waits for it. Launches alternate between the counters and
+ * each deep pass zeroes the other one (no memset per launch). */
+static int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const uint8_t *src, const uint64_t *in_off,
+                       uint64_t n, dg_tget_rec *rec, uint64_t *val_off, uint32_t *val_len, hipStream_t s,
+                       uint64_t max_len)
+{
+    if (n == 0) return DG_OK;
+    if (!src || !in_off || !rec) return set_err(DG_E_INVALID, "null buffer");
+    if ((uintptr_t)rec & 15) return set_err(DG_E_INVALID, "records not 16-byte aligned"); /* one store each */
+    const uint64_t pairs = n * ps->hdr.n_paths;
+    if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
+        return set_err(DG_E_INVALID, "batch of %llu messages x %u paths", (unsigned long long)n, ps->hdr.n_paths);
+    if (!c->ws_tget) {
+        HIPCHK(hipMalloc(&c->ws_tget, TGET_WS));
+        HIPCHK(hipMalloc(&c->tget_cnt, 16));
+        HIPCHK(hipMemset(c->tget_cnt, 0, 16));
+        HIPCHK(hipDeviceSynchronize()); /* before a non-blocking stream counts on it */
+        HIPCHK(hipEventCreateWithFlags(&c->tget_done, hipEventDisableTiming | hipEventDisableSystemFence));
+    }
+    if (c->tget_list_cap < pairs) { /* the previous launch may still fill the old list */
+        if (c->tget_last) HIPCHK(hipEventSynchronize(c->tget_done));
+        int rc = grow(c->tget_list, c->tget_list_cap, pairs);
+        if (rc) return rc;
+    }
+    if (c->tget_last && c->tget_last != s) HIPCHK(hipStreamWaitEvent(s, c->tget_done, 0));
+    TGParams A;
+    memset(&A, 0, sizeof A);
+    A.src = src;
+    A.in_off = in_off;
+    A.pairs = pairs;
+    A.P = ps->hdr.n_paths;
+    A.root_type = root_type;
+    A.blob = ps->d_blob;
+    A.off_steps = ps->hdr.off_steps;
+    A.off_pool = ps->hdr.off_pool;
+    A.rec = rec;
+    A.val_off = val_off;
+    A.val_len = val_len;
+    A.deep_list = c->tget_list;
+    A.deep_count = c->tget_cnt + c->tget_set;
+    A.reset_count = c->tget_cnt + (c->tget_set ^ 1u);
+    A.ws = (uint64_t *)(void *)c->ws_tget;
+    launch_tget_pass(s, A, tget_spread(c, max_len));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        launch_tget_deep(s, A);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) c->tget_set ^= 1u;
+    else (void)hipMemsetAsync(c->tget_cnt, 0, 16, s); /* the deep pass may not have run: both cleared */
+    HIPCHK(hipEventRecord(c->tget_done, s));
+    c->tget_last = s;
+    if (e != hipSuccess) return set_err(DG_E_HIP, "tget launch: %s", hipGetErrorString(e));
+    return DG_OK;
+}
+
+extern "C" {
+
+int dg_path_create(dg_ctx *c, const void *blob, size_t len, dg_path **out)
+{
+    if (!c || !blob || !out) return set_err(DG_E_INVALID, "null ctx/blob/out");
+    if (len < sizeof(dg_path_hdr)) return set_err(DG_E_ARG, "path blob of %zu bytes: no header", len);
+    dg_path_hdr h;
+    memcpy(&h, blob, sizeof h);
+    if (h.magic != DG_PATH_MAGIC || h.version != DG_PATH_VERSION)
+        return set_err(DG_E_ARG, "path blob: bad magic or version (%08x, %u)", h.magic, h.version);
+    if (h.n_paths < 1 || h.n_paths > DG_TGET_MAX_PATHS)
+        return set_err(DG_E_ARG, "path blob: %u paths (1 to %u)", h.n_paths, DG_TGET_MAX_PATHS);
+    if (h.total_len > len || (h.off_steps & 7) || (h.off_pool & 7) ||
+        h.off_steps < sizeof(dg_path_hdr) + (uint64_t)h.n_paths * sizeof(dg_path_ent) ||
+        (uint64_t)h.off_steps + (uint64_t)h.n_steps * sizeof(dg_path_step) > h.off_pool ||
+        (uint64_t)h.off_pool + h.pool_len != h.total_len)
+        return set_err(DG_E_ARG, "path blob: tables outside the blob");
+    const uint8_t *b = (const uint8_t *)blob;
+    for (uint32_t k = 0; k < h.n_paths; k++) {
+        dg_path_ent pe;
+        memcpy(&pe, b + sizeof(dg_path_hdr) + k * sizeof(dg_path_ent), sizeof pe);
+        if (pe.count > DG_TGET_MAX_STEPS)
+            return set_err(DG_E_ARG, "path %u: %u steps (at most %u)", k, pe.count, DG_TGET_MAX_STEPS);
+        if ((uint64_t)pe.first + pe.count > h.n_steps) return set_err(DG_E_ARG, "path %u: steps outside the table", k);
+        for (uint32_t s = 0; s < pe.count; s++) {
+            dg_path_step st;
+            memcpy(&st, b + h.off_steps + (uint64_t)(pe.first + s) * sizeof(dg_path_step), sizeof st);
+            const bool key = st.kind == DG_PS_STRKEY || st.kind == DG_PS_BINKEY;
+            if (st.kind < DG_PS_FIELD || st.kind > DG_PS_BINKEY)
+                return set_err(DG_E_ARG, "path %u step %u: unknown kind %u", k, s, st.kind);
+            if (st.kind == DG_PS_FIELD && (st.val < -32768 || st.val > 32767))
+                return set_err(DG_E_ARG, "path %u step %u: field id %lld outside int16", k, s, (long long)st.val);
+            if (st.kind == DG_PS_INDEX && st.val < 0)
+                return set_err(DG_E_ARG, "path %u step %u: negative index %lld", k, s, (long long)st.val);
+            if (key && (st.val < 0 || (uint64_t)st.val + st.key_len > h.pool_len))
+                return set_err(DG_E_ARG, "path %u step %u: key outside the pool", k, s);
+            if (!key && st.key_len) return set_err(DG_E_ARG, "path %u step %u: key_len on a keyless step", k, s);
+        }
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t *p;
+    HIPCHK(hipMalloc(&p, (size_t)h.total_len + 16)); /* keys are compared 16 bytes at a time */
+    hipError_t e = hipMemcpy(p, blob, h.total_len, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(p + h.total_len, 0, 16);
+    if (e == hipSuccess) e = hipDeviceSynchronize(); /* before launches on non-blocking streams read it */
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return set_err(DG_E_HIP, "path upload: %s", hipGetErrorString(e));
+    }
+    dg_path *ps = new dg_path();
+    ps->ctx = c;
+    ps->d_blob = p;
+    ps->hdr = h;
+    *out = ps;
+    return DG_OK;
+}
+
+void dg_path_destroy(dg_path *p)
+{
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> g(p->ctx->mu);
+        (void)hipSetDevice(p->ctx->device);
+        (void)hipFree(p->d_blob);
+    }
+    delete p;
+}
+
+uint32_t dg_path_count(const dg_path *p) { return p ? p->hdr.n_paths : 0; }
+
+int dg_tget_batch_device(dg_ctx *c, const dg_path *ps, uint8_t root_type, const uint8_t *d_thrift,
+                         const uint64_t *d_in_off, uint64_t n, dg_tget_rec *d_rec, uint64_t *d_val_off,
+                         uint32_t *d_val_len, void *stream, uint64_t max_len)
+{
+    if (!c || !ps || ps->ctx != c) return set_err(DG_E_INVALID, "null ctx/paths, or paths of another context");
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return tget_launch(c, ps, root_type, d_thrift, d_in_off, n, d_rec, d_val_off, d_val_len, s, max_len);
+}
+
+int dg_tget_batch_host(dg_ctx *c, const dg_path *ps, uint8_t root_type, const uint8_t *thrift, const uint64_t *in_off,
+                       uint64_t n, dg_tget_rec *rec)
+{
+    if (!c || !ps || ps->ctx != c) return set_err(DG_E_INVALID, "null ctx/paths, or paths of another context");
+    if (n == 0) return DG_OK;
+    if (!thrift || !in_off || !rec) return set_err(DG_E_INVALID, "null buffer");
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    const uint64_t base = in_off[0], total = in_off[n] - base, pairs = n * ps->hdr.n_paths;
+    std::vector<uint64_t> io(n + 1);
+    uint64_t max_len = 0;
+    for (uint64_t i = 0; i <= n; i++) {
+        if (in_off[i] < base || (i && in_off[i] < in_off[i - 1])) return set_err(DG_E_INVALID, "in_off not ascending");
+        io[i] = in_off[i] - base;
+        if (i) max_len = std::max<uint64_t>(max_len, io[i] - io[i - 1]);
+    }
+    int rc;
+    hipStream_t s = c->stream;
+    if ((rc = grow(c->d_json, c->d_json_cap, total + 64))) return rc;
+    if ((rc = grow(c->d_in_off, c->d_in_cap, n + 1))) return rc;
+    if ((rc = grow(c->d_out, c->d_out_cap, pairs * sizeof(dg_tget_rec) + 64))) return rc;
+    if (total) HIPCHK(hipMemcpyAsync(c->d_json, thrift + base, total, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c->d_json + total, 0, 64, s));
+    HIPCHK(hipMemcpyAsync(c->d_in_off, io.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s)); /* io is a local */
+    if ((rc = tget_launch(c, ps, root_type, c->d_json, c->d_in_off, n, (dg_tget_rec *)(void *)c->d_out, nullptr,
+                          nullptr, s, max_len)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(rec, c->d_out, pairs * sizeof(dg_tget_rec), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DG_OK;
+}
+
+}  // extern "C"

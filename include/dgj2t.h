@@ -79,6 +79,8 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *   "t2j_spread"  DG_T2J_SPREAD   0 auto, 1, 2 or 4 lanes per t2j message
  *   "t2j_wave_min" DG_T2J_WAVE_MIN t2j messages longer than this take the t2j wave kernel (512; 0 never)
  *   "flat_wrap"   DG_FLAT_WRAP    -1 auto, 0 off: the flat kernel for {"key":{flat}} members of a non-flat root
+ *   "tget_spread" DG_TGET_SPREAD  0 auto, 1, 2 or 4: every how-manieth lane of the path-lookup kernel takes a
+ *                                 (message, path) pair
  * Unknown names return DG_E_INVALID. Thread-safe (the context lock). */
 int dg_ctx_set_knob(dg_ctx *ctx, const char *name, int64_t value);
 int dg_ctx_get_knob(dg_ctx *ctx, const char *name, int64_t *value);
@@ -449,6 +451,90 @@ int dg_t2j_batch_device_cb(dg_ctx *ctx, const dg_desc *desc, uint32_t root_type,
 int dg_t2j_batch_host_cb(dg_ctx *ctx, const dg_desc *desc, uint32_t root_type, const uint8_t *thrift,
                          const uint64_t *in_off, uint64_t n, uint64_t opts, uint8_t *out, uint64_t out_cap,
                          uint64_t *out_off, uint64_t *ret, uint64_t *out_need, uint64_t *aux, const dg_cb_tables *cb);
+
+/*
+ * tget: batched GetByPath over Thrift-binary messages (the reference's
+ * thrift/generic Node.GetByPath / Value.GetByPath, node.go:292-484 and
+ * value.go:70-161): the byte span of a sub-value, found by walking field
+ * headers and skipping values, nothing else decoded. A path set (1 to
+ * DG_TGET_MAX_PATHS paths of up to DG_TGET_MAX_STEPS steps, blob layout in
+ * dgj2t_defs.h under DG_PATH_MAGIC) is validated and uploaded once, then
+ * evaluated for every message of a batch in one launch.
+ *
+ * The create call returns DG_E_ARG (text in dg_last_error) for a blob that
+ * breaks a limit: no path or more than 8, more than 16 steps in a path, an
+ * unknown step kind, a field id outside int16, a negative index, a key outside
+ * the pool, a table outside the blob. A path set belongs to its context and is
+ * read-only after creation (any number of launches may share it); destroy it
+ * only after the launches that use it have finished.
+ */
+typedef struct dg_path dg_path;
+int dg_path_create(dg_ctx *ctx, const void *blob, size_t len, dg_path **out);
+void dg_path_destroy(dg_path *p);
+uint32_t dg_path_count(const dg_path *p);
+
+/* One result: path k on message i is rec[i * P + k], P = the set's path
+ * count. Offsets are relative to the message's first byte (messages of 4 GiB
+ * or more are DG_TGET_E_READ, aux = 0xFFFFFFFF). By status (dgj2t_defs.h):
+ *   DG_TGET_OK         [start, end) = the sub-value, type = its wire type
+ *                      (the field header's, or the container header's element
+ *                      type; root_type for the empty path, whose span is the
+ *                      whole top value); step = the path length; aux = 0.
+ *   DG_TGET_NOT_FOUND  step = the step that missed; end = start; a FIELD step:
+ *                      type STRUCT, start 0; an INDEX step: type LIST or SET,
+ *                      start = the offset after the list header; a key step:
+ *                      type MAP, start = the offset after the map header.
+ *                      aux = the read offset at the miss (after the STOP byte,
+ *                      the list header, or the map's last entry).
+ *                      LIST and SET share one wire form: type is LIST when the
+ *                      wire type of the last field header the path went
+ *                      through (root_type when it went through none) is LIST,
+ *                      else SET. This is Value.GetByPath's rule (value.go:122,
+ *                      131); Node.GetByPath tests the ROOT node's type at every
+ *                      field step (node.go:456, a slip) and is not followed.
+ *   DG_TGET_E_READ     meta.ErrRead: a short buffer, an invalid wire type in a
+ *                      field, list or map header, a negative container size, a
+ *                      negative or over-long string size, skip depth beyond
+ *                      1023. step = the step that failed, the path length for
+ *                      the final skip; start = end = type = aux = 0.
+ *   DG_TGET_E_TYPE     meta.ErrDismatchType: a STRKEY step on a map whose key
+ *                      type is not STRING, an INTKEY step on one whose key
+ *                      type is not I08, I16, I32 or I64. step = that step, aux
+ *                      = the map's key type; start = end = type = 0.
+ * A step applied to a value of another shape (INDEX on a struct, ...) is no
+ * error in the reference: the bytes are read as the header the step expects,
+ * and so here. An INTKEY on an I08-keyed map compares the key byte UNSIGNED
+ * (ReadInt returns int(byte), thrift/binary.go:739-741): -1 never hits, 255
+ * hits the byte 0xFF. */
+typedef struct dg_tget_rec {
+    uint32_t start, end;
+    uint8_t type, status;
+    uint16_t step;
+    uint32_t aux;
+} dg_tget_rec; /* 16 bytes */
+
+/* Device buffers, stream-ordered, async (stream NULL: the context's). Message
+ * i is d_thrift[d_in_off[i], d_in_off[i+1]); no byte past d_in_off[i+1] counts
+ * as part of it. The arena is readable 16 bytes past its last message.
+ * root_type: the wire type of each message's top value (12 = STRUCT as a rule;
+ * LIST, SET and MAP roots are legal). d_rec: n * P records, 16-byte aligned
+ * (each is one 16-byte store). d_val_off (u64)
+ * and d_val_len (u32), n * P entries each, may be NULL: they receive
+ * d_in_off[i] + start and end - start (length 0 unless DG_TGET_OK), the
+ * (slot offset, length) arrays dg_pack_device_scan takes to pack the found
+ * values of a P = 1 run back to back. max_len: the batch's longest message
+ * (0 = unknown), a hint for the lane spacing (dense lanes measured fastest at
+ * ~100 B and at ~1.2 KB, so every length takes them today; the tget_spread
+ * knob forces another). n = 0 returns DG_OK and launches
+ * nothing; n * P must stay below 2^32. A value nested deeper than the kernel's
+ * 8 LDS skip frames is rerun on device with 1024 frames in device memory;
+ * past 1023 levels the reference fails too (DG_TGET_E_READ). */
+int dg_tget_batch_device(dg_ctx *ctx, const dg_path *paths, uint8_t root_type, const uint8_t *d_thrift,
+                         const uint64_t *d_in_off, uint64_t n, dg_tget_rec *d_rec, uint64_t *d_val_off,
+                         uint32_t *d_val_len, void *stream, uint64_t max_len);
+/* Host buffers, synchronous: thrift[in_off[i], in_off[i+1]), rec n * P. */
+int dg_tget_batch_host(dg_ctx *ctx, const dg_path *paths, uint8_t root_type, const uint8_t *thrift,
+                       const uint64_t *in_off, uint64_t n, dg_tget_rec *rec);
 
 /* Timing helper for benchmarks: launch the device batch `iters` times on the
  * context stream bracketed by HIP events; returns total milliseconds of GPU

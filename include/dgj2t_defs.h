@@ -118,6 +118,57 @@ typedef struct dg_cb_tables {
 #define DG_E_NOMEM (-3)
 #define DG_E_DESC (-4)
 #define DG_E_AGAIN (-5) /* dg_agg_submit(nonblock): no open batch right now */
+#define DG_E_ARG (-6)   /* a path-set blob that breaks the layout or a limit below */
+
+/* tget (batched GetByPath, include/dgj2t.h): per-record statuses */
+#define DG_TGET_OK 0
+#define DG_TGET_NOT_FOUND 1 /* errNotFound */
+#define DG_TGET_E_READ 2    /* meta.ErrRead */
+#define DG_TGET_E_TYPE 3    /* meta.ErrDismatchType */
+
+/* Path-set blob: everything little-endian, tables 8-aligned.
+ *
+ *   offset 0             dg_path_hdr (32 bytes)
+ *   offset 32            n_paths x dg_path_ent (8 bytes each)
+ *   offset off_steps     n_steps x dg_path_step (16 bytes each)
+ *   offset off_pool      pool_len key bytes (STRKEY / BINKEY), unpadded and
+ *                        back to back; the pool is the blob's last part
+ *   total_len            = off_pool + pool_len, at most the length passed
+ *
+ * Path k owns steps [first, first + count) of the step table; count may be 0
+ * (the empty path: the whole top value). Limits: 1 <= n_paths <=
+ * DG_TGET_MAX_PATHS; count <= DG_TGET_MAX_STEPS; first + count <= n_steps;
+ * off_steps >= 32 + 8 n_paths; off_steps and off_pool multiples of 8;
+ * off_steps + 16 n_steps <= off_pool.
+ * A step, by kind (the reference's PathType of the same name):
+ *   DG_PS_FIELD   val = the field id, -32768..32767        (PathFieldId)
+ *   DG_PS_INDEX   val = the index, >= 0                     (PathIndex)
+ *   DG_PS_STRKEY  key bytes pool[val, val + key_len)        (PathStrKey)
+ *   DG_PS_INTKEY  val = the key, any int64                  (PathIntKey)
+ *   DG_PS_BINKEY  key bytes pool[val, val + key_len): the key's Thrift-binary
+ *                 encoding as it stands in the message      (PathBinKey)
+ * key_len is 0 for the other kinds; val + key_len <= pool_len for keys.
+ * PathFieldName has no wire form: the host resolves names to ids through the
+ * IDL first, as Value.GetByPath does (thrift/generic/value.go:123-131). */
+#define DG_PATH_MAGIC 0x31504744u /* "DGP1" */
+#define DG_PATH_VERSION 1u
+#define DG_TGET_MAX_PATHS 8u
+#define DG_TGET_MAX_STEPS 16u
+#define DG_PS_FIELD 1u
+#define DG_PS_INDEX 2u
+#define DG_PS_STRKEY 3u
+#define DG_PS_INTKEY 4u
+#define DG_PS_BINKEY 5u
+typedef struct dg_path_hdr {
+    uint32_t magic, version, total_len, n_paths, n_steps, off_steps, off_pool, pool_len;
+} dg_path_hdr;
+typedef struct dg_path_ent {
+    uint32_t first, count;
+} dg_path_ent;
+typedef struct dg_path_step {
+    uint32_t kind, key_len;
+    int64_t val;
+} dg_path_step;
 
 /* t2j (Thrift binary -> JSON, conv/t2j) option bits: the conv.Options fields
  * conv/t2j/impl.go reads (conv/api.go:52-121) */
