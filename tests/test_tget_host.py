@@ -9,6 +9,7 @@ import struct
 import pytest
 
 import t2jgen
+import tgetgen
 import tgetref as R
 from conftest import GOLDEN
 from dynamicgo_amd import generic as G
@@ -92,22 +93,28 @@ def test_checker_skip_matches_compiled_reference():
     st = (_SkipBuf * 1024)()
     rng = random.Random(1234)
     td = t2jgen.all_types_desc()
-    fields = 0
-    for _ in range(256):
-        m = t2jgen.gen_thrift(rng, td)
+
+    def both(m):
         pr = R.Proto(m)
         pr.skip_type(R.STRUCT)
         assert pr.read == len(m) == lib.tb_skip(st, m, len(m), R.STRUCT)
         pr = R.Proto(m)
+        fields = 0
         while True:
             t, _ = pr.read_field_begin()
             if t == R.STOP:
-                break
+                return fields
             at = pr.read
             pr.skip_type(t)
             assert pr.read - at == lib.tb_skip(st, m[at:], len(m) - at, t), (t, at)
             fields += 1
-    assert fields > 2000
+
+    assert sum(both(t2jgen.gen_thrift(rng, td)) for _ in range(256)) > 2000
+    # chains of every container kind (tgetgen.chain_message), 0 to 12 levels: far below either skipper's depth rule
+    rng = random.Random(5)
+    for d in range(13):
+        for _ in range(16):
+            assert both(tgetgen.chain_message(*tgetgen.random_chain(rng, d))) == 2
 
 
 def test_blob_layout():
