@@ -101,7 +101,14 @@ uint32_t dg_desc_root(const dg_desc *desc);
  *   d_json      JSON arena (at least in_off[n] + 16 readable bytes)
  *   d_in_off    n+1 u64 offsets into d_json; message i = [in_off[i], in_off[i+1])
  *   d_out       output arena; message i may use [out_off[i], out_off[i+1])
- *   d_out_off   n+1 u64 slot bounds (e.g. prefix sum of dg_slot_bound(len))
+ *   d_out_off   n+1 u64 slot bounds (e.g. prefix sum of dg_slot_bound(len)).
+ *               A slot may start at any byte and have any size, 0 included:
+ *               the kernels write [out_off[i], out_off[i+1]) and nothing else
+ *               (the wave and flat kernels' writers store the partial words
+ *               at both ends of what they own byte-exactly; the lane writer
+ *               stores whole words only at an 8-aligned base and bytes
+ *               otherwise). 8-aligned bases are the fast case, not a
+ *               requirement.
  *   d_out_len   n u32: Thrift bytes written for message i (0 on error; for
  *               DG_ST_OUT_OVERFLOW: the bytes the message needs)
  *   d_ret       n u64: packed reference status (0 = ok), or DG_ST_OUT_OVERFLOW
