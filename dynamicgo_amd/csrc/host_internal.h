@@ -1,7 +1,10 @@
 /*
- * host_internal.h — what the C-ABI translation units share: the context,
- * descriptor and per-stream scratch records and the error helpers
- * (j2t_host.hip defines the functions, t2j_host.hip uses them).
+ * host_internal.h — what the C-ABI translation units share: the owners of
+ * GPU resources (device and pinned arrays, events, streams), the rule that
+ * orders a shared buffer across streams, the context, descriptor and
+ * per-stream scratch records, the entry guard, the argument records of one
+ * batch and the error helpers (j2t_host.hip defines the functions; t2j_host,
+ * tget_host and j2t_pipe use them).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +13,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -23,61 +27,226 @@ __attribute__((visibility("hidden"))) int set_err(int code, const char *fmt, ...
         if (e_ != hipSuccess) return set_err(DG_E_HIP, "%s: %s", #x, hipGetErrorString(e_));  \
     } while (0)
 
+/* ---- owners: move-only, freed by their destructors and nowhere else. hipFree
+ * and hipHostFree wait for the whole device, so an owner frees only when it
+ * dies or when grow() finds it too small: a buffer that fits is reused. ---- */
+
+/* what DevArr and PinArr share: pointer + capacity (in elements) */
+template <class T, hipError_t (*FREE)(void *)>
+struct ArrBase {
+    T *p = nullptr;
+    uint64_t cap = 0;
+    ArrBase() = default;
+    ArrBase(ArrBase &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    ArrBase &operator=(ArrBase &&o) noexcept
+    {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~ArrBase() { reset(); }
+    void reset()
+    {
+        if (p) (void)FREE(p);
+        p = nullptr, cap = 0;
+    }
+    operator T *() const { return p; }
+};
+
+/* device memory. grow: free first, then max(want, 2 cap) elements */
+template <class T>
+struct DevArr : ArrBase<T, hipFree> {
+    int alloc(uint64_t n) /* exactly n elements, once */
+    {
+        HIPCHK(hipMalloc(&this->p, n * sizeof(T)));
+        this->cap = n;
+        return DG_OK;
+    }
+    int grow(uint64_t want)
+    {
+        if (this->cap >= want) return DG_OK;
+        const uint64_t nc = std::max<uint64_t>(want, this->cap * 2);
+        this->reset();
+        return alloc(nc);
+    }
+};
+
+/* pinned host memory, grown on demand (hipHostMalloc is slow: keep it) */
+template <class T>
+struct PinArr : ArrBase<T, hipHostFree> {
+    int alloc(uint64_t n, unsigned flags = hipHostMallocDefault)
+    {
+        HIPCHK(hipHostMalloc((void **)&this->p, n * sizeof(T), flags));
+        this->cap = n;
+        return DG_OK;
+    }
+    int grow(uint64_t want) /* like DevArr::grow, and at least 64 KiB */
+    {
+        if (this->cap >= want) return DG_OK;
+        const uint64_t nc = std::max<uint64_t>(std::max<uint64_t>(want, this->cap * 2), (1 << 16) / sizeof(T));
+        this->reset();
+        /* DG_HOST_NUMA=1: on the allocating thread's NUMA node (its policy)
+         * instead of the driver's default placement */
+        static const unsigned fl = getenv("DG_HOST_NUMA") ? hipHostMallocNumaUser : hipHostMallocDefault;
+        return alloc(nc, fl);
+    }
+};
+
+/* what Event and Stream share: a HIP handle destroyed with its owner */
+template <class H, hipError_t (*DESTROY)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle &operator=(Handle &&o) noexcept
+    {
+        std::swap(h, o.h);
+        return *this;
+    }
+    ~Handle()
+    {
+        if (h) (void)DESTROY(h);
+    }
+    operator H() const { return h; }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    hipError_t create() { return hipEventCreate(&h); } /* a timing event */
+    hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&h, flags); }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+    hipError_t create(unsigned flags) { return hipStreamCreateWithFlags(&h, flags); }
+};
+
+/* The ordering rule of everything several streams share (a scratch, a
+ * per-context workspace): `done` is recorded on the stream that used it
+ * last, and a launch on another stream waits for it first. The event orders
+ * execution only -- no host reads data through it, and a kernel's own
+ * dispatch fences already publish its writes to the kernels after it -- so
+ * it carries no system-scope fence: that fence cost every batch a 5-6 us gap
+ * before the stream's next kernel (r8g trace; r8h/r8i: C2 in flight 336 ->
+ * 353 GB/s; a device-scope release instead gained nothing). */
+struct StreamOrder {
+    Event done;                 /* created by the first acquire */
+    hipStream_t last = nullptr; /* stream of the last launch that used it (null: none pending) */
+    hipError_t acquire(hipStream_t s)
+    {
+        if (!done) {
+            hipError_t e = done.create(hipEventDisableTiming | hipEventDisableSystemFence);
+            if (e != hipSuccess) return e;
+        }
+        return last && last != s ? hipStreamWaitEvent(s, done, 0) : hipSuccess;
+    }
+    hipError_t publish(hipStream_t s)
+    {
+        hipError_t e = hipEventRecord(done, s);
+        if (e == hipSuccess) last = s;
+        return e;
+    }
+    /* the host waits for the last launch (before a buffer it may read goes) */
+    hipError_t wait_host() const { return last ? hipEventSynchronize(done) : hipSuccess; }
+    /* streams s[0..n) are about to be destroyed and the device is idle */
+    void forget(const hipStream_t *s, int n)
+    {
+        if (std::find(s, s + n, last) != s + n) last = nullptr;
+    }
+};
+
+/* one workspace per context, shared across streams (t2j's deep frames and
+ * token regions, tget's frames); ws is freed before done is destroyed */
+struct SharedWs : StreamOrder {
+    DevArr<uint8_t> ws;
+};
+
+/* Two counter sets used by alternate launches: each launch counts in mine()
+ * and its deep pass zeroes other(), the set the previous launch used (no
+ * memset per launch). finish: flip after a good launch; after a failed one
+ * the deep pass may not have run, so both sets are cleared on the stream. */
+struct AltCounters {
+    uint32_t *set[2] = {nullptr, nullptr};
+    uint32_t bytes = 0, cur = 0;
+    uint32_t *mine() const { return set[cur]; }
+    uint32_t *other() const { return set[cur ^ 1u]; }
+    void finish(bool ok, hipStream_t s)
+    {
+        if (ok) cur ^= 1u;
+        else
+            for (uint32_t *p : set) (void)hipMemsetAsync(p, 0, bytes, s);
+    }
+};
+
+/* Scratch::counts: DG_NCOUNTS u32 counters, each owned by ONE path.
+ * j2t: [CNT_BAIL .. CNT_DEEP_DONE] are reset by the launch's last kernel
+ *      (list mode), or by a stream memset of DG_J2T_COUNTS_BYTES when an
+ *      enqueue fails half way;
+ * pack: CNT_PACK is dg_pack_device_scan's arrivals, the next its departures,
+ *      [12] its slot-overflow count (MsgFrame::ovf_out) -- self-reset;
+ * t2j: launches alternate between the sets at CNT_T2J_A and CNT_T2J_B
+ *      (Scratch::t2j_cnt); within a set, the T2J_* offsets. */
+enum : uint32_t {
+    CNT_BAIL = 0,      /* bails */
+    CNT_BIG = 1,       /* large messages */
+    CNT_WAVEQ = 2,     /* wave queue */
+    CNT_HUGE = 3,      /* huge messages */
+    CNT_DEEP = 4,      /* deep count */
+    CNT_DEEP_DONE = 5, /* blocks done (deep pass) */
+    CNT_PACK = 6,
+    CNT_T2J_A = 8,
+    CNT_T2J_B = 16,
+    T2J_DEEPQ = 0, /* deep-pass queue length */
+    T2J_BIG = 1,   /* long messages */
+    T2J_WAVEQ = 2, /* the wave kernel's queue */
+    T2J_BAIL = 3,  /* its bails */
+};
+constexpr uint32_t DG_NCOUNTS = 24;
+constexpr uint32_t DG_J2T_COUNTS_BYTES = 6 * 4;
+constexpr uint32_t FRAME_CAP = 4096;
+
 /* Device scratch of one launch pipeline: the bail/big lists, their
  * self-resetting counters, the wave queue and the workspaces. Launches on the
  * SAME stream reuse it in stream order. Each stream a caller passes gets its
  * own scratch (up to DG_MAX_SCRATCH per context), so concurrent streams never
  * share lists or counters; past that cap a scratch is shared and the next
- * launch on another stream waits for its previous launch (hipStreamWaitEvent
- * on `done`), which keeps the ordering rule true in every case. */
+ * launch on another stream waits for its previous launch (StreamOrder), which
+ * keeps the ordering rule true in every case.
+ * Destruction: the host waits for the last launch and for the side stream,
+ * then the members go in reverse order: buffers, side events, side stream,
+ * `done`. */
 constexpr int DG_MAX_SCRATCH = 40; /* an aggregator ring (<= AGG_RING_MAX = 24 streams) + the context's stream
                                     * + the in-flight side streams (<= 7) + the host pipeline's 3 */
-constexpr uint32_t DG_NCOUNTS = 24;
-constexpr uint32_t DG_J2T_COUNTS_BYTES = 6 * 4;
-constexpr uint32_t DG_T2J_DEEP_COUNT = 8;
-struct Scratch {
-    hipStream_t owner = nullptr;   /* the stream it was created for */
-    hipStream_t last = nullptr;    /* stream of the last launch that used it */
-    bool used = false;
-    hipEvent_t done = nullptr;     /* recorded after every launch that used it (no system-scope fence: ordering only) */
-    uint8_t *ws_fast = nullptr;
-    uint64_t ws_fast_lanes = 0;
-    uint64_t *d_deep_list = nullptr;
-    /* DG_NCOUNTS u32 counters, each owned by ONE path:
-     * j2t: [0] bails, [1] large messages, [2] wave queue, [3] huge messages,
-     *      [4] deep count, [5] blocks done (deep pass) -- [0..5] are reset by
-     *      the launch's last kernel (list mode), or by a stream memset of
-     *      DG_J2T_COUNTS_BYTES when an enqueue fails half way;
-     * pack: [6] arrivals, [7] departures of dg_pack_device_scan, [12] its
-     *      slot-overflow count (MsgFrame::ovf_out) -- self-reset;
-     * t2j: [8] deep-pass queue length, [9] long messages, [10] the wave
-     *      kernel's queue, [11] its bails; launches alternate between this
-     *      set and [16..19] (t2j_set), and each launch's deep pass zeroes the
-     *      other set, the one the previous launch used (no memset per
-     *      launch). */
-    uint32_t *d_counts = nullptr;
-    uint32_t *d_bail_list = nullptr;
-    uint64_t bail_cap = 0;
-    uint32_t *d_big_list = nullptr;
-    uint64_t big_cap = 0;
-    uint8_t *ws_wave = nullptr;
-    uint8_t *ws_deep = nullptr;
-    uint64_t *d_sums = nullptr;    /* dg_pack_device_scan: per-block byte totals (n_cu) */
-    uint8_t *d_frame = nullptr;    /* dg_pack_device_framed: header + footer bytes */
-    std::vector<uint8_t> frame;    /* what d_frame holds */
-    uint32_t *t2j_list = nullptr;  /* t2j: messages queued for the deep pass ([8] of d_counts counts them) */
-    uint64_t t2j_list_cap = 0;
-    uint32_t *t2j_big = nullptr;   /* t2j: long messages for the wave kernel ([9] counts them, [10] its queue) */
-    uint64_t t2j_big_cap = 0;
-    uint32_t *t2j_bail = nullptr;  /* t2j: the wave kernel's bails ([11] counts them) */
-    uint64_t t2j_bail_cap = 0;
-    uint32_t t2j_set = 0;          /* t2j: the counter set of the next launch (0: [8..11], 1: [16..19]) */
+struct Scratch : StreamOrder {
+    hipStream_t owner = nullptr; /* the stream it was created for */
     /* a second stream of this scratch's launches (created on first use): the
      * t2j wave kernel runs on it beside the lane pass (Knobs::t2j_overlap) */
-    hipStream_t side = nullptr;
-    hipEvent_t side_go = nullptr, side_done = nullptr;
+    Stream side;
+    Event side_done, side_go;
+    DevArr<uint8_t> ws_fast; /* ws_fast_lanes lanes; deep_list grows with it */
+    uint64_t ws_fast_lanes = 0;
+    DevArr<uint64_t> deep_list;
+    DevArr<uint32_t> counts;
+    DevArr<uint32_t> bail_list, big_list;
+    DevArr<uint8_t> ws_wave, ws_deep;
+    DevArr<uint64_t> sums;      /* dg_pack_device_scan: per-block byte totals (n_cu) */
+    DevArr<uint8_t> d_frame;    /* dg_pack_device_framed: header + footer bytes */
+    std::vector<uint8_t> frame; /* what d_frame holds */
+    DevArr<uint32_t> t2j_list;  /* t2j: messages queued for the deep pass */
+    DevArr<uint32_t> t2j_big;   /* t2j: long messages for the wave kernel */
+    DevArr<uint32_t> t2j_bail;  /* t2j: the wave kernel's bails */
+    AltCounters t2j_cnt;
+    ~Scratch()
+    {
+        (void)wait_host();
+        if (side) (void)hipStreamSynchronize(side);
+    }
+    /* grow a scratch buffer: the old one may still be read by the scratch's
+     * previous launch, so wait for it before freeing */
+    template <class T>
+    int grow(DevArr<T> &a, uint64_t want)
+    {
+        if (a.cap >= want) return DG_OK;
+        HIPCHK(wait_host());
+        return a.grow(want);
+    }
 };
-constexpr uint32_t FRAME_CAP = 4096;
 
 /* routing knobs: env at dg_ctx_create, then dg_ctx_set_knob (include/dgj2t.h) */
 struct Knobs {
@@ -93,140 +262,166 @@ struct Knobs {
     int64_t tget_spread = 0;    /* tget: lanes per (message, path) pair, 0 = from the longest message (tget_host.hip) */
 };
 
+/* one chunk in flight of dg_j2t_pipeline_host (j2t_pipe.hip) */
+struct PipeBuf;
+struct PipeBufDelete {
+    void operator()(PipeBuf *p) const;
+};
+
+/* Destruction order is part of the behaviour. ~dg_ctx selects the device and
+ * synchronises the context's stream; then the members go in reverse order of
+ * declaration, which is why they are declared in this order: the pipeline's
+ * chunks (each synchronises its own stream, then frees) and its staging, the
+ * scratches (before any stream they were last used on: an event last recorded
+ * on a destroyed stream is not safe to wait on), the staging buffers, the
+ * shared workspaces, the in-flight side streams and their events, and the
+ * context's own stream last. */
 struct dg_ctx {
-    int device;
-    hipStream_t stream;
+    int device = 0;
+    Stream stream;
     int n_cu = 0;
     Knobs knobs;
-    uint32_t *d_pending = nullptr;
-    unsigned long long *d_stats = nullptr; /* {bails, deeps} since the last dg_ctx_stats reset */
-    std::vector<Scratch *> scratch;
     uint32_t rr = 0; /* round-robin pick once DG_MAX_SCRATCH scratches exist */
     std::mutex mu;
-    /* staging for the host API */
-    uint8_t *d_json = nullptr; uint64_t d_json_cap = 0;
-    uint64_t *d_in_off = nullptr; uint64_t d_in_cap = 0;
-    uint8_t *d_out = nullptr; uint64_t d_out_cap = 0;
-    uint64_t *d_out_off = nullptr; uint64_t d_oo_cap = 0;
-    uint32_t *d_out_len = nullptr; uint64_t d_ol_cap = 0;
-    uint64_t *d_ret = nullptr; uint64_t d_ret_cap = 0;
-    uint64_t *d_aux = nullptr; uint64_t d_aux_cap = 0;       /* t2j: per-message response-base spans */
-    uint8_t *d_cb = nullptr; uint64_t d_cb_cap = 0;          /* t2j: callback answers (entries + bytes) */
-    uint8_t *d_pack = nullptr; uint64_t d_pack_cap = 0;      /* packed Thrift (dg_pack_device_scan) */
-    uint64_t *d_pack_off = nullptr; uint64_t d_po_cap = 0;
-    uint8_t *h_up = nullptr; uint64_t h_up_cap = 0;          /* pinned: offsets + JSON, one H2D */
-    uint8_t *h_down = nullptr; uint64_t h_down_cap = 0;      /* pinned: ret + out_len (+ packed bytes) */
-    /* t2j deep pass: T2J_DEEP_DEPTH frames per lane, ONE per context (about
-     * 100 MB, allocated by the first t2j launch), ordered across streams by
-     * ws_t2j_done recorded after each deep pass on ws_t2j_last */
-    uint8_t *ws_t2j = nullptr;
-    hipEvent_t ws_t2j_done = nullptr;
-    hipStream_t ws_t2j_last = nullptr;
-    /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB), one
-     * per context, ordered across streams like ws_t2j */
-    uint8_t *ws_t2w = nullptr;
-    hipEvent_t ws_t2w_done = nullptr;
-    hipStream_t ws_t2w_last = nullptr;
-    /* tget (tget_host.hip): the deep pass's frames (32 MB, allocated by the
-     * first lookup), its queue and the two alternating queue counters, one per
-     * context, ordered across streams by tget_done recorded on tget_last */
-    uint8_t *ws_tget = nullptr;
-    uint32_t *tget_cnt = nullptr;
-    uint32_t *tget_list = nullptr; uint64_t tget_list_cap = 0;
-    uint32_t tget_set = 0;
-    hipEvent_t tget_done = nullptr;
-    hipStream_t tget_last = nullptr;
-    /* dg_j2t_pipeline_host: its per-chunk buffers (j2t_pipe.hip PipeBuf),
-     * kept across calls; pipe_mu serialises pipeline calls */
-    std::mutex pipe_mu;
-    std::vector<void *> pipe;
-    uint8_t *h_pipe_out = nullptr; uint64_t h_pipe_out_cap = 0; /* pinned staging when the caller's */
-    uint8_t *h_pipe_aux = nullptr; uint64_t h_pipe_aux_cap = 0; /* buffers are pageable */
-    uint8_t *h_pipe_ovf = nullptr; uint64_t h_pipe_ovf_cap = 0; /* pipeline: slot overflows per chunk (pinned) */
-    uint64_t *d_zero = nullptr;                                 /* 8 zero bytes (device) */
-    uint64_t *d_pipe_cur = nullptr; uint64_t pipe_cur_cap = 0;  /* pipeline: chunk k's start in out (device) */
-    /* dg_j2t_batch_device_inflight: the context's extra streams and their
-     * fork/join events (created on first use) */
-    std::vector<hipStream_t> side;
-    std::vector<hipEvent_t> side_ev;
-    hipEvent_t fork_ev = nullptr;
     /* dg_j2t_batch_device_ktime: while set, enqueue() records kt[0] before the
      * batch's first kernel, kt[1] after it, kt[2] after the wave kernel and
      * kt[3] after the list pass (timing events, on the launch stream) */
-    hipEvent_t *kt = nullptr;
+    const Event *kt = nullptr;
+    /* dg_j2t_batch_device_inflight: the context's extra streams and their
+     * fork/join events (created on first use) */
+    Event fork_ev;
+    std::vector<Event> side_ev;
+    std::vector<Stream> side;
+    /* tget (tget_host.hip): the deep pass's frames (32 MB, allocated by the
+     * first lookup), its queue and the two alternating queue counters */
+    SharedWs tget;
+    DevArr<uint32_t> tget_list, tget_cnt_buf;
+    AltCounters tget_cnt;
+    /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB) */
+    SharedWs t2j_tok;
+    /* t2j deep pass: T2J_DEEP_DEPTH frames per lane (about 100 MB, allocated
+     * by the first t2j launch) */
+    SharedWs t2j_deep;
+    /* staging for the host API */
+    PinArr<uint8_t> h_down;     /* pinned: ret + out_len (+ packed bytes) */
+    PinArr<uint8_t> h_up;       /* pinned: offsets + JSON, one H2D */
+    DevArr<uint64_t> d_pack_off;
+    DevArr<uint8_t> d_pack;     /* packed Thrift (dg_pack_device_scan) */
+    DevArr<uint8_t> d_cb;       /* t2j: callback answers (entries + bytes) */
+    DevArr<uint64_t> d_aux;     /* t2j: per-message response-base spans */
+    DevArr<uint64_t> d_ret;
+    DevArr<uint32_t> d_out_len;
+    DevArr<uint64_t> d_out_off;
+    DevArr<uint8_t> d_out;
+    DevArr<uint64_t> d_in_off;
+    DevArr<uint8_t> d_json;
+    DevArr<unsigned long long> d_stats; /* {bails, deeps} since the last dg_ctx_stats reset */
+    DevArr<uint64_t> d_zero;            /* 8 zero bytes (device) */
+    DevArr<uint32_t> d_pending;
+    std::vector<std::unique_ptr<Scratch>> scratch;
+    /* dg_j2t_pipeline_host: its per-chunk buffers, kept across calls; pipe_mu
+     * serialises pipeline calls */
+    std::mutex pipe_mu;
+    PinArr<uint8_t> h_pipe_aux, h_pipe_out; /* pinned staging when the caller's buffers are pageable */
+    PinArr<uint8_t> h_pipe_ovf;             /* slot overflows per chunk (pinned) */
+    DevArr<uint64_t> d_pipe_cur;            /* chunk k's start in out (device) */
+    std::vector<std::unique_ptr<PipeBuf, PipeBufDelete>> pipe;
+    ~dg_ctx()
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
-/* frees the context's pipeline buffers (j2t_pipe.hip) */
-__attribute__((visibility("hidden"))) void dg_i_pipe_free(dg_ctx *c);
-
-/* pinned host staging, grown on demand (hipHostMalloc is slow: keep it) */
-static inline int grow_pinned(uint8_t *&p, uint64_t &cap, uint64_t want)
-{
-    if (cap >= want) return DG_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    uint64_t nc = std::max<uint64_t>(want, cap * 2);
-    nc = std::max<uint64_t>(nc, 1 << 16);
-    /* DG_HOST_NUMA=1: on the allocating thread's NUMA node (its policy)
-     * instead of the driver's default placement */
-    static const unsigned fl = getenv("DG_HOST_NUMA") ? hipHostMallocNumaUser : hipHostMallocDefault;
-    HIPCHK(hipHostMalloc((void **)&p, nc, fl));
-    cap = nc;
-    return DG_OK;
-}
+/* What every entry point does first: the null checks (`ok` carries the
+ * entry's own), the context lock, the device, the stream's default.
+ *   Entry g(c, c && d, stream); if (g.rc) return g.rc; */
+struct Entry {
+    std::unique_lock<std::mutex> lk;
+    hipStream_t s = nullptr;
+    int rc = DG_OK;
+    Entry(dg_ctx *c, bool ok, void *stream = nullptr, const char *what = "bad args")
+    {
+        if (!ok) {
+            rc = set_err(DG_E_INVALID, "%s", what);
+            return;
+        }
+        lk = std::unique_lock<std::mutex>(c->mu);
+        const hipError_t e = hipSetDevice(c->device);
+        if (e != hipSuccess) rc = set_err(DG_E_HIP, "hipSetDevice(c->device): %s", hipGetErrorString(e));
+        s = stream ? (hipStream_t)stream : (hipStream_t)c->stream;
+    }
+};
 
 struct dg_desc {
-    dg_ctx *ctx;
-    uint8_t *d_blob;
-    size_t len;
+    dg_ctx *ctx = nullptr;
+    DevArr<uint8_t> d_blob;
+    size_t len = 0;
     dg_desc_hdr hdr;
-    uint8_t *d_side = nullptr;     /* t2j side table (dg_desc_attach_t2j) */
-    std::vector<uint8_t> hblob;    /* host copy of the blob (launch decisions) */
+    DevArr<uint8_t> d_side;     /* t2j side table (dg_desc_attach_t2j) */
+    std::vector<uint8_t> hblob; /* host copy of the blob (launch decisions) */
     size_t side_len = 0;
 };
 
-template <class T>
-static inline int grow(T *&p, uint64_t &cap, uint64_t want)
-{
-    if (cap >= want) return DG_OK;
-    (void)hipFree(p);
-    p = nullptr;
-    uint64_t nc = std::max<uint64_t>(want, cap * 2);
-    HIPCHK(hipMalloc(&p, nc * sizeof(T)));
-    cap = nc;
-    return DG_OK;
-}
+/* the callback answers of a batch (dg_cb_tables, dgj2t_defs.h): HTTP-mapping
+ * entries (DG_F_HM_SPLIT) and value-mapping entries; all null when absent */
+struct HMIn {
+    const dg_hm_entry *tab = nullptr;
+    uint32_t n_hm = 0;
+    const uint8_t *bytes = nullptr;
+    const dg_cb_entry *vm = nullptr; /* t2j: the answer entries */
+};
 
-/* grow a scratch buffer: the old one may still be read by the scratch's
- * previous launch, so wait for it before freeing */
-template <class T>
-static inline int grow_x(Scratch *x, T *&p, uint64_t &cap, uint64_t want)
-{
-    if (cap >= want) return DG_OK;
-    if (x->used) HIPCHK(hipEventSynchronize(x->done));
-    return grow(p, cap, want);
-}
+/* one batch, either direction: device pointers at the launches, host
+ * pointers at the host entry points (there `ret` and `aux` are the caller's) */
+struct BatchArgs {
+    const uint8_t *src = nullptr; /* JSON (j2t), Thrift (t2j) */
+    const uint64_t *in_off = nullptr;
+    uint64_t n = 0, flags = 0;    /* flags: DG_F_* (j2t), DG_T2J_* options (t2j) */
+    uint8_t *out = nullptr;
+    const uint64_t *out_off = nullptr;
+    uint32_t *out_len = nullptr;
+    uint64_t *ret = nullptr;
+    uint32_t *pending = nullptr;
+    uint64_t max_len = 0;         /* the longest message, 0: unknown */
+    HMIn hm;
+    uint64_t *aux = nullptr;      /* t2j: per-message response-base spans */
+};
+
+/* where a host entry point leaves its results (the caller's pageable memory) */
+struct HostOut {
+    uint8_t *out;
+    uint64_t out_cap;
+    uint64_t *out_off, *out_need;
+};
+
+/* the optional chaining of a packing (dg_i_convert_pack): positions start at
+ * *base_in, bytes past dst_cap are not written (0: no limit); base_mod16 =
+ * 1 | phase << 1: positions start at (*base_in + phase) & 15 instead.
+ * ret_dst (optional): the status words copied there. cur_out (device,
+ * optional): the end position (the next chunk's base). ovf_out (optional,
+ * e.g. pinned): the count of DG_ST_OUT_OVERFLOW messages. The packing waits
+ * for pack_after (another stream's event) when it is set. */
+struct PackChain {
+    const uint64_t *base_in = nullptr;
+    uint64_t dst_cap = 0;
+    int base_mod16 = 0;
+    uint64_t *ret_dst = nullptr, *cur_out = nullptr, *ovf_out = nullptr;
+    hipEvent_t pack_after = nullptr;
+};
 
 /* before streams s[0..n) are destroyed: the device is synchronized, the
- * scratches they own are freed, and no other scratch keeps one of them as
- * the stream of its last launch (takes the ctx mutex) */
+ * scratches they own are freed, and nothing shared keeps one of them as the
+ * stream of its last launch (takes the ctx mutex) */
 __attribute__((visibility("hidden"))) void dg_i_scratch_release(dg_ctx *c, const hipStream_t *s, int n);
 
 /* the scratch for a launch on stream s (ctx mutex held) */
 __attribute__((visibility("hidden"))) int scratch_for(dg_ctx *c, hipStream_t s, Scratch **out);
 
 /* one batch converted and packed on stream s (takes the ctx mutex): message
- * i's Thrift at d_packed + d_pack_off[i], d_pack_off[n] = total; failed and
- * overflowed messages pack as nothing (their d_ret says why). Chained form:
- * positions start at *base_in, bytes past dst_cap are not written (0: no
- * limit); d_packed / d_pack_off may be pinned host memory; the packing
- * waits for pack_after (another stream's event) when it is set. base_mod16
- * = 1 | phase << 1: positions start at (*base_in + phase) & 15 instead.
- * cur_out (device, optional): the end position (the next chunk's base).
- * ovf_out (optional, e.g. pinned): the count of DG_ST_OUT_OVERFLOW messages. */
-__attribute__((visibility("hidden"))) int dg_i_convert_pack(
-    dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_json, const uint64_t *d_in_off, uint64_t n,
-    uint64_t flags, uint8_t *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, uint8_t *d_packed,
-    uint64_t *d_pack_off, hipStream_t s, uint64_t max_len, const uint64_t *base_in = nullptr, uint64_t dst_cap = 0,
-    hipEvent_t pack_after = nullptr, int base_mod16 = 0, uint64_t *ret_dst = nullptr, uint64_t *cur_out = nullptr,
-    uint64_t *ovf_out = nullptr);
+ * i's Thrift at packed + pack_off[i], pack_off[n] = total; failed and
+ * overflowed messages pack as nothing (their ret says why). packed /
+ * pack_off may be pinned host memory. */
+__attribute__((visibility("hidden"))) int dg_i_convert_pack(dg_ctx *c, const dg_desc *d, uint32_t root,
+                                                            const BatchArgs &b, uint8_t *packed, uint64_t *pack_off,
+                                                            hipStream_t s, const PackChain &ch);

@@ -35,92 +35,44 @@ static const uint64_t FAST_WS_STRIDE = DCAP + WS_KEYCAP + (uint64_t)WS_REQCAP * 
 static const uint64_t DEEP_WS_STRIDE = DCAP + DEEP_KEYCAP + (uint64_t)DEEP_REQCAP * 8 +
                                        (uint64_t)MAX_RECURSE * sizeof(Frame) + MAX_RECURSE / 8;
 
-static void scratch_free(Scratch *x)
+static int scratch_new(dg_ctx *c, hipStream_t owner, std::unique_ptr<Scratch> &out)
 {
-    if (!x) return;
-    if (x->used) (void)hipEventSynchronize(x->done);
-    (void)hipFree(x->ws_fast);
-    (void)hipFree(x->d_deep_list);
-    (void)hipFree(x->d_counts);
-    (void)hipFree(x->d_bail_list);
-    (void)hipFree(x->d_big_list);
-    (void)hipFree(x->ws_wave);
-    (void)hipFree(x->ws_deep);
-    (void)hipFree(x->d_sums);
-    (void)hipFree(x->d_frame);
-    (void)hipFree(x->t2j_list);
-    (void)hipFree(x->t2j_big);
-    (void)hipFree(x->t2j_bail);
-    if (x->side) (void)hipStreamSynchronize(x->side);
-    if (x->side_go) (void)hipEventDestroy(x->side_go);
-    if (x->side_done) (void)hipEventDestroy(x->side_done);
-    if (x->side) (void)hipStreamDestroy(x->side);
-    if (x->done) (void)hipEventDestroy(x->done);
-    delete x;
-}
-
-static int scratch_new(dg_ctx *c, hipStream_t owner, Scratch **out)
-{
-    Scratch *x = new Scratch();
+    std::unique_ptr<Scratch> x(new Scratch());
     x->owner = owner;
-    /* `done` orders execution only: the host frees or overwrites a scratch
-     * buffer after it, and a launch on another stream that takes the scratch
-     * over waits for it. No host reads data through it, and a kernel's own
-     * dispatch fences already publish its writes to the kernels after it (as
-     * between the batch's kernels on one stream), so it carries no
-     * system-scope fence: that fence cost every batch a 5-6 us gap before the
-     * stream's next kernel (r8g trace; r8h/r8i: C2 in flight 336 -> 353 GB/s;
-     * a device-scope release instead gained nothing). */
-    hipError_t e = hipEventCreateWithFlags(&x->done, hipEventDisableTiming | hipEventDisableSystemFence);
-    if (e == hipSuccess) e = hipMalloc(&x->d_counts, DG_NCOUNTS * 4);
+    int rc = x->counts.alloc(DG_NCOUNTS);
     /* ordered before the owner stream's launches: a plain hipMemset runs on
      * the null stream, which a non-blocking stream (the aggregator's) does
      * not wait for -- its first batch then read uninitialised list counters
      * and left messages unconverted (ret 0, no bytes) */
-    if (e == hipSuccess) e = hipMemsetAsync(x->d_counts, 0, DG_NCOUNTS * 4, owner);
-    if (e == hipSuccess) e = hipMalloc(&x->ws_deep, DEEP_WS_STRIDE * DEEP_THREADS);
-    if (e == hipSuccess) e = hipMalloc(&x->ws_wave, (size_t)c->n_cu * std::max(WV_BLOCKS_PER_CU, WV5_BLOCKS_PER_CU) * WV_WAVES * DCAP);
-    if (e == hipSuccess) e = hipMalloc(&x->d_sums, (size_t)c->n_cu * 8);
-    if (e == hipSuccess) e = hipMalloc(&x->d_frame, FRAME_CAP);
-    if (e != hipSuccess) {
-        scratch_free(x);
-        return set_err(DG_E_HIP, "scratch allocation: %s", hipGetErrorString(e));
-    }
-    *out = x;
+    if (!rc) HIPCHK(hipMemsetAsync(x->counts, 0, DG_NCOUNTS * 4, owner));
+    if (!rc) rc = x->ws_deep.alloc(DEEP_WS_STRIDE * DEEP_THREADS);
+    if (!rc) rc = x->ws_wave.alloc((size_t)c->n_cu * std::max(WV_BLOCKS_PER_CU, WV5_BLOCKS_PER_CU) * WV_WAVES * DCAP);
+    if (!rc) rc = x->sums.alloc((size_t)c->n_cu);
+    if (!rc) rc = x->d_frame.alloc(FRAME_CAP);
+    if (rc) return rc;
+    x->t2j_cnt.set[0] = x->counts + CNT_T2J_A;
+    x->t2j_cnt.set[1] = x->counts + CNT_T2J_B;
+    x->t2j_cnt.bytes = 16;
+    out = std::move(x);
     return DG_OK;
 }
 
 void dg_i_scratch_release(dg_ctx *c, const hipStream_t *s, int n)
 {
     if (!c || n <= 0) return;
-    std::lock_guard<std::mutex> g(c->mu);
-    (void)hipSetDevice(c->device);
+    Entry g(c, true);
     (void)hipDeviceSynchronize(); /* nothing is pending on any scratch after this */
-    std::vector<Scratch *> keep;
-    for (Scratch *x : c->scratch) {
-        bool owned = false, last = false;
-        for (int k = 0; k < n; k++) {
-            owned |= x->owner == s[k];
-            last |= x->last == s[k];
-        }
-        if (owned) {
-            x->used = false; /* done (synchronized): scratch_free waits on nothing */
-            scratch_free(x);
-            continue;
-        }
-        if (last) {
-            x->used = false;
-            x->last = nullptr;
-        }
-        keep.push_back(x);
+    for (auto &x : c->scratch) {
+        x->forget(s, n);
+        if (std::find(s, s + n, x->owner) == s + n) continue;
+        x->last = nullptr; /* done (synchronized): ~Scratch waits on nothing */
+        x.reset();
     }
-    c->scratch.swap(keep);
+    c->scratch.erase(std::remove(c->scratch.begin(), c->scratch.end(), nullptr), c->scratch.end());
     c->rr = 0;
-    for (int k = 0; k < n; k++) { /* the t2j workspaces' last streams */
-        if (c->ws_t2j_last == s[k]) c->ws_t2j_last = nullptr;
-        if (c->ws_t2w_last == s[k]) c->ws_t2w_last = nullptr;
-        if (c->tget_last == s[k]) c->tget_last = nullptr;
-    }
+    c->t2j_deep.forget(s, n);
+    c->t2j_tok.forget(s, n);
+    c->tget.forget(s, n);
 }
 
 /* The scratch for a launch on stream s (ctx mutex held); orders s after the
@@ -128,18 +80,20 @@ void dg_i_scratch_release(dg_ctx *c, const hipStream_t *s, int n)
 int scratch_for(dg_ctx *c, hipStream_t s, Scratch **out)
 {
     Scratch *x = nullptr;
-    for (Scratch *y : c->scratch)
-        if (y->owner == s) x = y;
+    for (auto &y : c->scratch)
+        if (y->owner == s) x = y.get();
     if (!x) {
         if ((int)c->scratch.size() < DG_MAX_SCRATCH) {
-            int rc = scratch_new(c, s, &x);
+            std::unique_ptr<Scratch> nx;
+            int rc = scratch_new(c, s, nx);
             if (rc) return rc;
-            c->scratch.push_back(x);
+            c->scratch.push_back(std::move(nx));
+            x = c->scratch.back().get();
         } else {
-            x = c->scratch[c->rr++ % c->scratch.size()];
+            x = c->scratch[c->rr++ % c->scratch.size()].get();
         }
     }
-    if (x->used && x->last != s) HIPCHK(hipStreamWaitEvent(s, x->done, 0));
+    HIPCHK(x->acquire(s));
     *out = x;
     return DG_OK;
 }
@@ -180,16 +134,16 @@ int dg_ctx_create(int device, dg_ctx **out)
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return set_err(DG_E_INVALID, "device %d out of range (%d)", device, ndev);
     HIPCHK(hipSetDevice(device));
-    dg_ctx *c = new dg_ctx();
+    std::unique_ptr<dg_ctx> c(new dg_ctx()); /* an early return frees what it holds so far */
     c->device = device;
     /* a blocking stream: ordered with the legacy default stream (handle 0), so
      * a caller passing stream NULL (torch's default stream) sees the results
      * in order */
-    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamDefault));
-    HIPCHK(hipMalloc(&c->d_pending, 16));
-    HIPCHK(hipMalloc(&c->d_zero, 16));
+    HIPCHK(c->stream.create(hipStreamDefault));
+    int rc;
+    if ((rc = c->d_pending.alloc(4)) || (rc = c->d_zero.alloc(2))) return rc;
     HIPCHK(hipMemset(c->d_zero, 0, 16));
-    HIPCHK(hipMalloc(&c->d_stats, 16 * 8));
+    if ((rc = c->d_stats.alloc(16))) return rc;
     HIPCHK(hipMemset(c->d_stats, 0, 16 * 8));
     HIPCHK(hipDeviceSynchronize()); /* the memsets done before any stream (blocking or not) uses the buffers */
     HIPCHK(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device));
@@ -201,9 +155,9 @@ int dg_ctx_create(int device, dg_ctx **out)
         {"DG_TGET_SPREAD", "tget_spread"}};
     for (const auto &e : envk) {
         const char *v = getenv(e.env);
-        if (v && *v) *knob_ref(c, e.name) = strtoll(v, nullptr, 10);
+        if (v && *v) *knob_ref(c.get(), e.name) = strtoll(v, nullptr, 10);
     }
-    *out = c;
+    *out = c.release();
     return DG_OK;
 }
 
@@ -227,54 +181,18 @@ int dg_ctx_get_knob(dg_ctx *c, const char *name, int64_t *value)
     return DG_OK;
 }
 
-void dg_ctx_destroy(dg_ctx *c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    dg_i_pipe_free(c);
-    for (Scratch *x : c->scratch) scratch_free(x);
-    c->scratch.clear();
-    (void)hipFree(c->d_pending);
-    (void)hipFree(c->d_zero);
-    (void)hipFree(c->d_stats);
-    (void)hipFree(c->d_json);
-    (void)hipFree(c->d_in_off);
-    (void)hipFree(c->d_out);
-    (void)hipFree(c->d_out_off);
-    (void)hipFree(c->d_out_len);
-    (void)hipFree(c->d_ret);
-    (void)hipFree(c->d_aux);
-    (void)hipFree(c->d_cb);
-    (void)hipFree(c->d_pack);
-    (void)hipFree(c->d_pack_off);
-    (void)hipHostFree(c->h_up);
-    (void)hipHostFree(c->h_down);
-    (void)hipFree(c->ws_t2j);
-    if (c->ws_t2j_done) (void)hipEventDestroy(c->ws_t2j_done);
-    (void)hipFree(c->ws_t2w);
-    if (c->ws_t2w_done) (void)hipEventDestroy(c->ws_t2w_done);
-    (void)hipFree(c->ws_tget);
-    (void)hipFree(c->tget_cnt);
-    (void)hipFree(c->tget_list);
-    if (c->tget_done) (void)hipEventDestroy(c->tget_done);
-    for (hipStream_t x : c->side) (void)hipStreamDestroy(x);
-    for (hipEvent_t e : c->side_ev) (void)hipEventDestroy(e);
-    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void dg_ctx_destroy(dg_ctx *c) { delete c; } /* the order: ~dg_ctx (host_internal.h) */
 
-void *dg_ctx_stream(dg_ctx *c) { return c ? (void *)c->stream : nullptr; }
+void *dg_ctx_stream(dg_ctx *c) { return c ? (void *)(hipStream_t)c->stream : nullptr; }
 
-static int desc_finish(dg_ctx *c, const dg_desc_hdr &h, uint8_t *d_blob, size_t len, const void *host_blob,
+static int desc_finish(dg_ctx *c, const dg_desc_hdr &h, DevArr<uint8_t> &d_blob, size_t len, const void *host_blob,
                        dg_desc **out)
 {
     if (h.magic != DG_DESC_MAGIC || h.version < 1 || h.version > DG_DESC_VERSION || h.total_len > len)
         return set_err(DG_E_DESC, "bad descriptor blob header");
     dg_desc *d = new dg_desc();
     d->ctx = c;
-    d->d_blob = d_blob;
+    d->d_blob = std::move(d_blob);
     d->len = len;
     d->hdr = h;
     d->hblob.assign((const uint8_t *)host_blob, (const uint8_t *)host_blob + h.total_len);
@@ -361,8 +279,8 @@ int dg_desc_create(dg_ctx *c, const void *blob, size_t len, dg_desc **out)
     memcpy(&h, blob, sizeof h);
     if (h.magic != DG_DESC_MAGIC || h.total_len > len) return set_err(DG_E_DESC, "bad descriptor blob");
     HIPCHK(hipSetDevice(c->device));
-    uint8_t *d_blob;
-    HIPCHK(hipMalloc(&d_blob, len));
+    DevArr<uint8_t> d_blob;
+    if (int rc = d_blob.alloc(len)) return rc;
     HIPCHK(hipMemcpy(d_blob, blob, len, hipMemcpyHostToDevice));
     return desc_finish(c, h, d_blob, len, blob, out);
 }
@@ -371,8 +289,8 @@ int dg_desc_create_device(dg_ctx *c, const void *d_src, size_t len, dg_desc **ou
 {
     if (!c || !d_src || !out || len < sizeof(dg_desc_hdr)) return set_err(DG_E_INVALID, "bad args");
     HIPCHK(hipSetDevice(c->device));
-    uint8_t *d_blob;
-    HIPCHK(hipMalloc(&d_blob, len));
+    DevArr<uint8_t> d_blob;
+    if (int rc = d_blob.alloc(len)) return rc;
     HIPCHK(hipMemcpy(d_blob, d_src, len, hipMemcpyDeviceToDevice));
     std::vector<uint8_t> hb(len);
     HIPCHK(hipMemcpy(hb.data(), d_blob, len, hipMemcpyDeviceToHost));
@@ -382,21 +300,14 @@ int dg_desc_create_device(dg_ctx *c, const void *d_src, size_t len, dg_desc **ou
     return desc_finish(c, h, d_blob, len, hb.data(), out);
 }
 
-void dg_desc_destroy(dg_desc *d)
-{
-    if (!d) return;
-    (void)hipFree(d->d_blob);
-    (void)hipFree(d->d_side);
-    delete d;
-}
+void dg_desc_destroy(dg_desc *d) { delete d; }
 
 uint32_t dg_desc_root(const dg_desc *d) { return d ? d->hdr.root_type : 0; }
 
 int dg_ctx_stats(dg_ctx *c, uint64_t *bails, uint64_t *deeps, int reset)
 {
-    if (!c) return set_err(DG_E_INVALID, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    Entry g(c, c, nullptr, "null ctx");
+    if (g.rc) return g.rc;
     HIPCHK(hipDeviceSynchronize());
     unsigned long long h[2];
     HIPCHK(hipMemcpy(h, c->d_stats, sizeof h, hipMemcpyDeviceToHost));
@@ -411,9 +322,8 @@ int dg_ctx_stats(dg_ctx *c, uint64_t *bails, uint64_t *deeps, int reset)
 
 int dg_ctx_counters(dg_ctx *c, uint64_t *out, int n, int reset)
 {
-    if (!c || !out || n < 0 || n > 16) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    Entry g(c, c && out && n >= 0 && n <= 16);
+    if (g.rc) return g.rc;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, c->d_stats, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (reset) {
@@ -428,39 +338,42 @@ int dg_ctx_counters(dg_ctx *c, uint64_t *out, int n, int reset)
  * to costs a line (C2: one line per message instead of two) */
 uint64_t dg_slot_bound(uint64_t len) { return (4 * len + 64 + 127) & ~127ull; }
 
+/* the lane workspace and the deep list grow together, by at least 65536
+ * lanes, after the scratch's previous launch is done with the old ones */
 static int ensure_fast_ws(Scratch *x, uint64_t lanes)
 {
     if (x->ws_fast_lanes >= lanes) return DG_OK;
-    if (x->used) HIPCHK(hipEventSynchronize(x->done));
-    (void)hipFree(x->ws_fast);
-    (void)hipFree(x->d_deep_list);
-    x->ws_fast = nullptr;
-    x->d_deep_list = nullptr;
+    HIPCHK(x->wait_host());
+    x->ws_fast.reset();
+    x->deep_list.reset();
     x->ws_fast_lanes = 0;
-    uint64_t want = std::max<uint64_t>(lanes, 1 << 16);
-    HIPCHK(hipMalloc(&x->ws_fast, want * FAST_WS_STRIDE));
-    HIPCHK(hipMalloc(&x->d_deep_list, want * 8));
+    const uint64_t want = std::max<uint64_t>(lanes, 1 << 16);
+    int rc;
+    if ((rc = x->ws_fast.alloc(want * FAST_WS_STRIDE)) || (rc = x->deep_list.alloc(want))) return rc;
     x->ws_fast_lanes = want;
     return DG_OK;
 }
 
-/* the host's callback answers of a batch (dg_cb_tables, dgj2t_defs.h):
- * HTTP-mapping entries (DG_F_HM_SPLIT) and value-mapping entries, device
- * pointers */
-struct HMIn {
-    const dg_hm_entry *tab;
-    uint32_t n_hm;
-    const uint8_t *bytes;
-    const dg_cb_entry *vm = nullptr;
-};
-
-static int enqueue(dg_ctx *c, Scratch *x, const dg_desc *d, uint32_t root, const uint8_t *json,
-                   const uint64_t *in_off, uint64_t n, uint64_t flags, uint8_t *out, const uint64_t *out_off,
-                   uint32_t *out_len, uint64_t *ret, uint32_t *pending, hipStream_t s, uint64_t max_len,
-                   const HMIn *hm)
+/* The kernels of one batch on stream s. The route is
+ *   1. a first kernel over every message: it converts what it can, lists its
+ *      declines (bail list) and, when a wave stage follows, the messages
+ *      longer than big_max (big list);
+ *   2. the wave stage: the wave kernel over the big list, one wavefront per
+ *      message; its declines join the bail list;
+ *   3. the list pass: the lane kernel in list mode, the exact machine on the
+ *      bail list; it resets the counters.
+ * small route (the small or the flat kernel first): the wave stage only when
+ * the batch may hold a long message, and the list pass keeps P.fast, so the
+ * first kernel's declines try the full fast path; its grid is list_blocks.
+ * lane route (the lane kernel first): always a wave stage, and a list pass
+ * of the exact machine alone on at most 32 blocks. Without a fast path or a
+ * wave kernel: the lane kernel alone. */
+static int enqueue(dg_ctx *c, Scratch *x, const dg_desc *d, uint32_t root, const BatchArgs &b, hipStream_t s)
 {
+    const uint64_t n = b.n, max_len = b.max_len;
     int rc = ensure_fast_ws(x, n);
     if (rc) return rc;
+    uint64_t flags = b.flags;
     const bool no_wave = (flags & DG_F_NO_WAVE_PATH) != 0;
     /* flat roots go to the field-major flat kernel when the batch's messages
      * fit it (max_len unknown: longer ones are listed for the wave kernel) */
@@ -473,10 +386,11 @@ static int enqueue(dg_ctx *c, Scratch *x, const dg_desc *d, uint32_t root, const
         if (c->kt) (void)hipEventRecord(c->kt[i], s);
     };
     flags &= ~(DG_F_NO_WAVE_PATH | DG_F_FLAT_PATH | DG_F_NO_FLAT_PATH);
+    uint32_t *const cnt = x->counts;
     Params P;
     P.root = root;
-    P.json = json;
-    P.in_off = in_off;
+    P.json = b.src;
+    P.in_off = b.in_off;
     P.n = n;
     P.flag = flags;
     P.list = nullptr;
@@ -487,163 +401,123 @@ static int enqueue(dg_ctx *c, Scratch *x, const dg_desc *d, uint32_t root, const
     P.big_max = 0;
     P.huge_count = nullptr;
     P.huge_min = WV_HUGE_MIN;
-    P.hm_tab = hm ? hm->tab : nullptr;
-    P.hm_bytes = hm ? hm->bytes : nullptr;
-    P.n_hm = hm ? hm->n_hm : 0;
-    P.ans_tab = hm ? hm->vm : nullptr;
-    P.out = out;
-    P.out_off = out_off;
-    P.out_len = out_len;
-    P.ret = ret;
-    P.pending = pending;
-    P.deep_count = x->d_counts + 4;
-    P.deep_list = x->d_deep_list;
+    P.hm_tab = b.hm.tab;
+    P.hm_bytes = b.hm.bytes;
+    P.n_hm = b.hm.n_hm;
+    P.ans_tab = b.hm.vm;
+    P.out = b.out;
+    P.out_off = b.out_off;
+    P.out_len = b.out_len;
+    P.ret = b.ret;
+    P.pending = b.pending;
+    P.deep_count = cnt + CNT_DEEP;
+    P.deep_list = x->deep_list;
     P.ws = x->ws_fast;
     P.ws_stride = FAST_WS_STRIDE;
     P.keycap = WS_KEYCAP;
     P.reqcap = WS_REQCAP;
     P.fast = d->hdr.version >= 2 && (flags & ~FAST_FLAGS) == 0;
     P.stats = c->d_stats;
-    uint64_t blocks = (n + LANE_BLOCK - 1) / LANE_BLOCK;
+    const uint64_t blocks = (n + LANE_BLOCK - 1) / LANE_BLOCK;
     DeepParams DP;
     DP.ws = x->ws_deep;
     DP.ws_stride = DEEP_WS_STRIDE;
     DP.keycap = DEEP_KEYCAP;
     DP.reqcap = DEEP_REQCAP;
-    DP.done = x->d_counts + 5;
+    DP.done = cnt + CNT_DEEP_DONE;
     DP.blob = d->d_blob;
     DP.hdr = d->hdr;
     const uint64_t big_max = (uint64_t)K.wave_min; /* messages longer than this go to the wave kernel */
+    const bool may_be_long = max_len == 0 || max_len > big_max;
     const bool wave = P.fast && !no_wave && d->hdr.total_len <= WV_DESC && d->hdr.total_len <= DESC_LDS_BYTES &&
-                      (max_len == 0 || max_len > big_max);
-    /* the wave kernel's instance: 4 waves/SIMD with 2 KiB message staging
-     * (C3 1.46 ms) beats the 5-wave one (96 VGPRs, 98 spilled, 128 B staging:
-     * 1.55 ms) since keys ride in their values' lanes; the wave_occ knob
-     * (4|5) forces one */
-    const bool wave5 = K.wave_occ == 5;
-    auto wave_launch = [&](hipStream_t st, const Params &Q, const WaveParams &W) {
-        const uint64_t bpc = wave5 ? WV5_BLOCKS_PER_CU : WV_BLOCKS_PER_CU;
-        const uint64_t wblocks = std::min<uint64_t>((n + WV_WAVES - 1) / WV_WAVES, (uint64_t)c->n_cu * bpc);
-        if (wave5) launch_wave_kernel5(dim3((uint32_t)wblocks), st, Q, W);
-        else launch_wave_kernel(dim3((uint32_t)wblocks), st, Q, W);
-    };
-    auto lane_launch = [&](dim3 g, const Params &Q) {
-        if (d->hdr.total_len <= DESC_LDS_BYTES) launch_lane_kernel_lds(g, s, Q, DP);
-        else launch_lane_kernel_glb(g, s, Q, DP);
+                      may_be_long;
+    auto lane_launch = [&](uint64_t grid, const Params &Q) {
+        if (d->hdr.total_len <= DESC_LDS_BYTES) launch_lane_kernel_lds(dim3((uint32_t)grid), s, Q, DP);
+        else launch_lane_kernel_glb(dim3((uint32_t)grid), s, Q, DP);
     };
     const int mpw = (int)K.small_mpw; /* 0: lane kernel (in-kernel exact machine) */
     const bool small = P.fast && !no_wave && mpw > 0 && d->hdr.total_len <= SM_DESC;
-    if (small) {
-        /* 1. small kernel: lane-per-message fast path; declines -> bail list,
-         *    messages longer than big_max -> big list (when the batch has any)
-         * 2. wave kernel over the big list
-         * 3. lane kernel in list mode: the exact machine on the bail list */
-        if ((rc = grow_x(x, x->d_bail_list, x->bail_cap, n))) return rc;
-        if ((rc = grow_x(x, x->d_big_list, x->big_cap, n))) return rc;
-        const bool need_wave = max_len == 0 || max_len > big_max;
-        Params P1 = P;
-        if (need_wave) {
-            P1.big_list = x->d_big_list;
-            P1.big_count = x->d_counts + 1;
-            P1.big_max = big_max;
-            P1.huge_count = x->d_counts + 3;
-        }
+    if (!small && !wave) {
+        mark(0);
+        lane_launch(blocks, P);
+        mark(1);
+        mark(2);
+        mark(3);
+        HIPCHK(hipGetLastError());
+        return DG_OK;
+    }
+    if ((rc = x->grow(x->bail_list, n))) return rc;
+    if ((rc = x->grow(x->big_list, n))) return rc;
+    const bool wave_stage = small ? may_be_long : true;
+    Params P1 = P; /* 1. the first kernel */
+    if (wave_stage) {
+        P1.big_list = x->big_list;
+        P1.big_count = cnt + CNT_BIG;
+        P1.big_max = big_max;
+        P1.huge_count = cnt + CNT_HUGE;
+    }
+    uint32_t inner = DG_NONE;
+    const uint64_t wrap_ok = (small && K.flat_wrap != 0 && !no_flat && !flat_root(d, root, flags))
+                                 ? wrap_root(d, root, flags, &inner)
+                                 : 0;
+    mark(0);
+    if (!small) {
+        lane_launch(blocks, P1);
+    } else if ((use_flat && flat_root(d, root, flags)) || wrap_ok) {
+        /* flat root struct: a lane group per message, a lane per field;
+         * or a root whose messages wrap one flat struct (FlatParams::wrap) */
+        FlatParams FP;
+        FP.blob = d->d_blob;
+        FP.hdr = d->hdr;
+        FP.bail_count = cnt + CNT_BAIL;
+        FP.bail_list = x->bail_list;
+        FP.wrap = wrap_ok ? 1u : 0u;
+        FP.wrap_inner = wrap_ok ? inner : 0u;
+        FP.wrap_ok = wrap_ok;
+        launch_flat_kernel(dim3((uint32_t)((n + FL_MPB - 1) / FL_MPB)), s, P1, FP);
+    } else {
         SmallParams S;
         S.blob = d->d_blob;
         S.hdr = d->hdr;
-        S.bail_count = x->d_counts;
-        S.bail_list = x->d_bail_list;
-        uint32_t inner = DG_NONE;
-        const uint64_t wrap_ok = (K.flat_wrap != 0 && !no_flat && !flat_root(d, root, flags))
-                                     ? wrap_root(d, root, flags, &inner)
-                                     : 0;
-        if ((use_flat && flat_root(d, root, flags)) || wrap_ok) {
-            /* flat root struct: a lane group per message, a lane per field;
-             * or a root whose messages wrap one flat struct (FlatParams::wrap) */
-            FlatParams FP;
-            FP.blob = d->d_blob;
-            FP.hdr = d->hdr;
-            FP.bail_count = x->d_counts;
-            FP.bail_list = x->d_bail_list;
-            FP.wrap = wrap_ok ? 1u : 0u;
-            FP.wrap_inner = wrap_ok ? inner : 0u;
-            FP.wrap_ok = wrap_ok;
-            mark(0);
-            launch_flat_kernel(dim3((uint32_t)((n + FL_MPB - 1) / FL_MPB)), s, P1, FP);
-        } else {
-            const uint64_t mpb = (uint64_t)SM_WAVES * (uint64_t)(mpw >= 64 ? 64 : mpw == 16 ? 16 : 32);
-            mark(0);
-            launch_small_kernel(mpw, dim3((uint32_t)((n + mpb - 1) / mpb)), s, P1, S);
-        }
-        HIPCHK(hipGetLastError());
-        mark(1);
-        if (need_wave) {
-            WaveParams W;
-            W.blob = d->d_blob;
-            W.hdr = d->hdr;
-            W.bail_count = x->d_counts;
-            W.bail_list = x->d_bail_list;
-            W.list = x->d_big_list;
-            W.list_count = x->d_counts + 1;
-            W.huge_count = x->d_counts + 3;
-            W.list_cap = n;
-            W.ws = x->ws_wave;
-            W.queue = x->d_counts + 2;
-            wave_launch(s, P, W);
-            HIPCHK(hipGetLastError());
-        }
-        mark(2);
-        Params P3 = P;
-        P3.list = x->d_bail_list;
-        P3.list_count = x->d_counts;
-        P3.reset2 = x->d_counts + 1; /* P3.fast stays set: the small kernel's declines try the full fast path */
-        const uint64_t lb = (uint64_t)std::max<int64_t>(1, K.list_blocks); /* list-pass grid */
-        lane_launch(dim3((uint32_t)std::min<uint64_t>(blocks, lb)), P3);
-        mark(3);
-    } else if (!wave) {
-        mark(0);
-        lane_launch(dim3((uint32_t)blocks), P);
-        mark(1);
-        mark(2);
-        mark(3);
-    } else {
-        /* 1. lane kernel: small messages (lane fast path + exact machine);
-         *    messages longer than big_max are listed for the wave kernel
-         * 2. wave kernel: the listed ones, one wavefront per message
-         * 3. lane kernel in list mode: the wave kernel's bails, exact machine */
-        if ((rc = grow_x(x, x->d_bail_list, x->bail_cap, n))) return rc;
-        if ((rc = grow_x(x, x->d_big_list, x->big_cap, n))) return rc;
-        Params P1 = P;
-        P1.big_list = x->d_big_list;
-        P1.big_count = x->d_counts + 1;
-        P1.big_max = big_max;
-        P1.huge_count = x->d_counts + 3;
-        mark(0);
-        lane_launch(dim3((uint32_t)blocks), P1);
-        HIPCHK(hipGetLastError());
-        mark(1);
+        S.bail_count = cnt + CNT_BAIL;
+        S.bail_list = x->bail_list;
+        const uint64_t mpb = (uint64_t)SM_WAVES * (uint64_t)(mpw >= 64 ? 64 : mpw == 16 ? 16 : 32);
+        launch_small_kernel(mpw, dim3((uint32_t)((n + mpb - 1) / mpb)), s, P1, S);
+    }
+    HIPCHK(hipGetLastError());
+    mark(1);
+    if (wave_stage) { /* 2. */
         WaveParams W;
         W.blob = d->d_blob;
         W.hdr = d->hdr;
-        W.bail_count = x->d_counts;
-        W.bail_list = x->d_bail_list;
-        W.list = x->d_big_list;
-        W.list_count = x->d_counts + 1;
-        W.huge_count = x->d_counts + 3;
+        W.bail_count = cnt + CNT_BAIL;
+        W.bail_list = x->bail_list;
+        W.list = x->big_list;
+        W.list_count = cnt + CNT_BIG;
+        W.huge_count = cnt + CNT_HUGE;
         W.list_cap = n;
         W.ws = x->ws_wave;
-        W.queue = x->d_counts + 2;
-        wave_launch(s, P, W);
+        W.queue = cnt + CNT_WAVEQ;
+        /* the wave kernel's instance: 4 waves/SIMD with 2 KiB message staging
+         * (C3 1.46 ms) beats the 5-wave one (96 VGPRs, 98 spilled, 128 B
+         * staging: 1.55 ms) since keys ride in their values' lanes; the
+         * wave_occ knob (4|5) forces one */
+        const bool wave5 = K.wave_occ == 5;
+        const uint64_t bpc = wave5 ? WV5_BLOCKS_PER_CU : WV_BLOCKS_PER_CU;
+        const dim3 wgrid((uint32_t)std::min<uint64_t>((n + WV_WAVES - 1) / WV_WAVES, (uint64_t)c->n_cu * bpc));
+        if (wave5) launch_wave_kernel5(wgrid, s, P, W);
+        else launch_wave_kernel(wgrid, s, P, W);
         HIPCHK(hipGetLastError());
-        mark(2);
-        Params P3 = P;
-        P3.list = x->d_bail_list;
-        P3.list_count = x->d_counts;
-        P3.reset2 = x->d_counts + 1;
-        P3.fast = 0;
-        lane_launch(dim3((uint32_t)std::min<uint64_t>(blocks, 32)), P3);
-        mark(3);
     }
+    mark(2);
+    Params P3 = P; /* 3. */
+    P3.list = x->bail_list;
+    P3.list_count = cnt + CNT_BAIL;
+    P3.reset2 = cnt + CNT_BIG;
+    if (!small) P3.fast = 0;
+    const uint64_t cap = small ? (uint64_t)std::max<int64_t>(1, K.list_blocks) : 32;
+    lane_launch(std::min<uint64_t>(blocks, cap), P3);
+    mark(3);
     HIPCHK(hipGetLastError());
     return DG_OK;
 }
@@ -652,21 +526,16 @@ static int enqueue(dg_ctx *c, Scratch *x, const dg_desc *d, uint32_t root, const
  * `done` event. If an enqueue fails half way, the counters the list-mode
  * launch would have reset are cleared on the stream, so the next launch on
  * this scratch starts clean. */
-static int launch(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *json, const uint64_t *in_off,
-                  uint64_t n, uint64_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
-                  uint64_t *ret, uint32_t *pending, hipStream_t s, uint64_t max_len = 0,
-                  const HMIn *hm = nullptr)
+static int launch(dg_ctx *c, const dg_desc *d, uint32_t root, const BatchArgs &b, hipStream_t s)
 {
-    if (n == 0) return DG_OK;
+    if (b.n == 0) return DG_OK;
     if (root >= d->hdr.n_types) return set_err(DG_E_INVALID, "root type %u out of range", root);
     Scratch *x;
     int rc = scratch_for(c, s, &x);
     if (rc) return rc;
-    rc = enqueue(c, x, d, root, json, in_off, n, flags, out, out_off, out_len, ret, pending, s, max_len, hm);
-    if (rc) (void)hipMemsetAsync(x->d_counts, 0, DG_J2T_COUNTS_BYTES, s);
-    HIPCHK(hipEventRecord(x->done, s));
-    x->used = true;
-    x->last = s;
+    rc = enqueue(c, x, d, root, b, s);
+    if (rc) (void)hipMemsetAsync(x->counts, 0, DG_J2T_COUNTS_BYTES, s);
+    HIPCHK(x->publish(s));
     return rc;
 }
 
@@ -674,22 +543,20 @@ int dg_j2t_batch_device(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_
                         uint64_t n, uint64_t flags, uint8_t *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
                         uint64_t *d_ret, uint32_t *d_pending, void *stream)
 {
-    if (!c || !d) return set_err(DG_E_INVALID, "null ctx/desc");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return launch(c, d, root, d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, s);
+    Entry g(c, c && d, stream, "null ctx/desc");
+    if (g.rc) return g.rc;
+    const BatchArgs b{d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending};
+    return launch(c, d, root, b, g.s);
 }
 
 int dg_j2t_batch_device_ml(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_json, const uint64_t *d_in_off,
                            uint64_t n, uint64_t flags, uint8_t *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
                            uint64_t *d_ret, uint32_t *d_pending, void *stream, uint64_t max_len)
 {
-    if (!c || !d) return set_err(DG_E_INVALID, "null ctx/desc");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return launch(c, d, root, d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, s, max_len);
+    Entry g(c, c && d, stream, "null ctx/desc");
+    if (g.rc) return g.rc;
+    const BatchArgs b{d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, max_len};
+    return launch(c, d, root, b, g.s);
 }
 
 int dg_j2t_batch_device_hm(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_json, const uint64_t *d_in_off,
@@ -697,26 +564,22 @@ int dg_j2t_batch_device_hm(dg_ctx *c, const dg_desc *d, uint32_t root, const uin
                            const uint8_t *d_hm_bytes, uint8_t *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
                            uint64_t *d_ret, uint32_t *d_pending, void *stream, uint64_t max_len)
 {
-    if (!c || !d || (d_hm_tab && n_hm && !d_hm_bytes)) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HMIn hm{d_hm_tab, n_hm, d_hm_bytes};
-    return launch(c, d, root, d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, s, max_len,
-                  d_hm_tab ? &hm : nullptr);
+    Entry g(c, c && d && !(d_hm_tab && n_hm && !d_hm_bytes), stream);
+    if (g.rc) return g.rc;
+    BatchArgs b{d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, max_len};
+    if (d_hm_tab) b.hm = HMIn{d_hm_tab, n_hm, d_hm_bytes};
+    return launch(c, d, root, b, g.s);
 }
 
 int dg_j2t_batch_device_cb(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_json, const uint64_t *d_in_off,
                            uint64_t n, uint64_t flags, const dg_cb_tables *cb, uint8_t *d_out, const uint64_t *d_out_off,
                            uint32_t *d_out_len, uint64_t *d_ret, uint32_t *d_pending, void *stream, uint64_t max_len)
 {
-    if (!c || !d || (cb && (cb->hm_tab || cb->ans_tab) && !cb->bytes)) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HMIn hm{cb ? cb->hm_tab : nullptr, cb ? cb->n_hm : 0u, cb ? cb->bytes : nullptr, cb ? cb->ans_tab : nullptr};
-    return launch(c, d, root, d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, s, max_len,
-                  cb ? &hm : nullptr);
+    Entry g(c, c && d && !(cb && (cb->hm_tab || cb->ans_tab) && !cb->bytes), stream);
+    if (g.rc) return g.rc;
+    BatchArgs b{d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, max_len};
+    if (cb) b.hm = HMIn{cb->hm_tab, cb->n_hm, cb->bytes, cb->ans_tab};
+    return launch(c, d, root, b, g.s);
 }
 
 int dg_j2t_batch_device_iters(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_json,
@@ -724,14 +587,11 @@ int dg_j2t_batch_device_iters(dg_ctx *c, const dg_desc *d, uint32_t root, const 
                               const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, uint32_t *d_pending,
                               void *stream, uint64_t max_len, int iters)
 {
-    if (!c || !d || iters < 0) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    for (int k = 0; k < iters; k++) {
-        int rc = launch(c, d, root, d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, s, max_len);
-        if (rc) return rc;
-    }
+    Entry g(c, c && d && iters >= 0, stream);
+    if (g.rc) return g.rc;
+    const BatchArgs b{d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, max_len};
+    for (int k = 0; k < iters; k++)
+        if (int rc = launch(c, d, root, b, g.s)) return rc;
     return DG_OK;
 }
 
@@ -740,24 +600,23 @@ int dg_j2t_batch_device_ktime(dg_ctx *c, const dg_desc *d, uint32_t root, const 
                               const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, uint32_t *d_pending,
                               void *stream, uint64_t max_len, int iters, double *ms)
 {
-    if (!c || !d || iters < 1 || !ms) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    std::vector<hipEvent_t> ev((size_t)iters * 4, nullptr);
+    Entry g(c, c && d && iters >= 1 && ms, stream);
+    if (g.rc) return g.rc;
+    const BatchArgs b{d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, max_len};
+    std::vector<Event> ev((size_t)iters * 4);
     int rc = DG_OK;
     /* timing events without the system-scope fence (HIP's flag for events
      * that only measure): with it each mark added the fence's L2 writeback to
      * the kernel before it (C2 flat kernel ~35.0 us against 33.1 under rocprof) */
     for (auto &e : ev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) rc = set_err(DG_E_HIP, "hipEventCreate");
+        if (e.create(hipEventDisableSystemFence) != hipSuccess) rc = set_err(DG_E_HIP, "hipEventCreate");
     for (int k = 0; k < iters && !rc; k++) {
         c->kt = &ev[(size_t)k * 4];
-        rc = launch(c, d, root, d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, d_pending, s, max_len);
+        rc = launch(c, d, root, b, g.s);
     }
     c->kt = nullptr;
     ms[0] = ms[1] = ms[2] = 0;
-    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(DG_E_HIP, "hipStreamSynchronize");
+    if (!rc && hipStreamSynchronize(g.s) != hipSuccess) rc = set_err(DG_E_HIP, "hipStreamSynchronize");
     for (int k = 0; k < iters && !rc; k++)
         for (int i = 0; i < 3; i++) {
             float t = 0;
@@ -765,8 +624,6 @@ int dg_j2t_batch_device_ktime(dg_ctx *c, const dg_desc *d, uint32_t root, const 
                 rc = set_err(DG_E_HIP, "hipEventElapsedTime");
             ms[i] += t / iters;
         }
-    for (auto &e : ev)
-        if (e) (void)hipEventDestroy(e);
     return rc;
 }
 
@@ -774,22 +631,22 @@ int dg_j2t_batch_device_inflight(dg_ctx *c, const dg_desc *d, uint32_t root, con
                                  const uint64_t *d_in_off, uint64_t n, uint64_t flags, const uint64_t *d_out_off,
                                  const dg_out_set *sets, int depth, void *stream, uint64_t max_len, int iters)
 {
-    if (!c || !d || !sets || depth < 1 || depth > 8 || iters < 0) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s0 = stream ? (hipStream_t)stream : c->stream;
-    const int used = std::min(depth, std::max(iters, 1));
-    while ((int)c->side.size() < used - 1) {
-        hipStream_t x;
-        hipEvent_t e;
-        HIPCHK(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence)); /* ordering only */
-        c->side.push_back(x);
-        c->side_ev.push_back(e);
-    }
+    Entry g(c, c && d && sets && depth >= 1 && depth <= 8 && iters >= 0, stream);
+    if (g.rc) return g.rc;
+    const hipStream_t s0 = g.s;
     /* fork / join events order the streams only (no host reads through them):
      * no system-scope fence, like the scratch's `done` */
-    if (!c->fork_ev) HIPCHK(hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming | hipEventDisableSystemFence));
+    const unsigned order_only = hipEventDisableTiming | hipEventDisableSystemFence;
+    const int used = std::min(depth, std::max(iters, 1));
+    while ((int)c->side.size() < used - 1) {
+        Stream x;
+        Event e;
+        HIPCHK(x.create(hipStreamNonBlocking));
+        HIPCHK(e.create(order_only));
+        c->side.push_back(std::move(x));
+        c->side_ev.push_back(std::move(e));
+    }
+    if (!c->fork_ev) HIPCHK(c->fork_ev.create(order_only));
     if (used > 1) { /* fork: the side streams start after what `stream` holds */
         HIPCHK(hipEventRecord(c->fork_ev, s0));
         for (int j = 0; j < used - 1; j++) HIPCHK(hipStreamWaitEvent(c->side[j], c->fork_ev, 0));
@@ -798,8 +655,8 @@ int dg_j2t_batch_device_inflight(dg_ctx *c, const dg_desc *d, uint32_t root, con
     for (int k = 0; k < iters && !rc; k++) {
         const int j = k % used;
         const dg_out_set &o = sets[j];
-        rc = launch(c, d, root, d_json, d_in_off, n, flags, o.d_out, d_out_off, o.d_out_len, o.d_ret, o.d_pending,
-                    j ? c->side[j - 1] : s0, max_len);
+        const BatchArgs b{d_json, d_in_off, n, flags, o.d_out, d_out_off, o.d_out_len, o.d_ret, o.d_pending, max_len};
+        rc = launch(c, d, root, b, j ? (hipStream_t)c->side[j - 1] : s0);
     }
     for (int j = 0; j < used - 1; j++) { /* join, also after an error */
         HIPCHK(hipEventRecord(c->side_ev[j], c->side[j]));
@@ -808,12 +665,17 @@ int dg_j2t_batch_device_inflight(dg_ctx *c, const dg_desc *d, uint32_t root, con
     return rc;
 }
 
-/* dg_pack_device_scan / _framed without the context lock (the caller holds it) */
-static int pack_scan_nolock(dg_ctx *c, const uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_len,
-                            const uint64_t *d_ret, uint64_t n, const uint8_t *hdr, uint32_t hdr_len, const uint8_t *ftr,
-                            uint32_t ftr_len, uint8_t *d_dst, uint64_t *d_dst_off, hipStream_t s,
-                            const uint64_t *base_in = nullptr, uint64_t dst_cap = 0, int base_mod16 = 0,
-                            uint64_t *ret_dst = nullptr, uint64_t *cur_out = nullptr, uint64_t *ovf_out = nullptr);
+/* a method's header and footer around every packed message (dg_pack_device_framed) */
+struct FrameIn {
+    const uint8_t *hdr, *ftr;
+    uint32_t hdr_len, ftr_len;
+};
+
+/* dg_pack_device_scan / _framed without the context lock (the caller holds
+ * it): b's out / out_off / out_len / n, and its ret when failed messages are
+ * to pack as nothing */
+static int pack_scan_nolock(dg_ctx *c, hipStream_t s, const BatchArgs &b, const FrameIn *f, uint8_t *d_dst,
+                            uint64_t *d_dst_off, const PackChain &ch = PackChain());
 
 /* Host batch: ONE pinned upload [in_off | out_off | JSON], the kernels, a
  * device packing pass (used slot prefixes back to back, failed messages
@@ -823,16 +685,19 @@ static int pack_scan_nolock(dg_ctx *c, const uint8_t *d_out, const uint64_t *d_o
  * one exact-size launch on the same staging. */
 static const uint64_t HOST_ONE_TRIP = 4ull << 20;
 
-static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *json, const uint64_t *in_off,
-                      uint64_t n, uint64_t flags, const HMIn *hm, uint64_t hm_len, uint8_t *out, uint64_t out_cap,
-                      uint64_t *out_off, uint64_t *ret, uint64_t *out_need)
-/* hm: host pointers (tab may be NULL with vm set, and the reverse) */
+static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const BatchArgs &in, uint64_t hm_len,
+                      const HostOut &o)
+/* in: host pointers (src, in_off, n, flags, ret, hm: tab may be NULL with vm set, and the reverse) */
 {
-    if (!c || !d || (!json && n) || !in_off || !out_off || (!ret && n)) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    const uint8_t *const json = in.src;
+    const uint64_t *const in_off = in.in_off, n = in.n;
+    uint8_t *const out = o.out;
+    uint64_t *const out_off = o.out_off, *const ret = in.ret;
+    const HMIn *const hm = in.hm.tab || in.hm.vm ? &in.hm : nullptr;
+    Entry g(c, c && d && (json || !n) && in_off && out_off && (ret || !n));
+    if (g.rc) return g.rc;
     int rc;
-    hipStream_t s = c->stream;
+    const hipStream_t s = g.s;
     const uint64_t base = in_off[0], bytes = in_off[n] - in_off[0];
     /* upload: [ioff (n+1) | soff (n+1) | HTTP-mapping table (n x n_hm),
      * value-mapping table (n), answer bytes (optional) | JSON + 64 zero bytes] */
@@ -841,7 +706,7 @@ static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t 
     const uint64_t hmb = hm ? (hm_len + 7) & ~7ull : 0;
     const uint64_t hmw = hm ? 2 * n * nhm + n * nvm + hmb / 8 : 0; /* words */
     const uint64_t up_bytes = 16 * (n + 1) + 8 * hmw + bytes + 64;
-    if ((rc = grow_pinned(c->h_up, c->h_up_cap, up_bytes))) return rc;
+    if ((rc = c->h_up.grow(up_bytes))) return rc;
     uint64_t *ioff = (uint64_t *)(void *)c->h_up, *soff = ioff + n + 1;
     uint64_t *hhm = soff + n + 1;
     uint8_t *hj = (uint8_t *)(void *)(hhm + hmw);
@@ -864,28 +729,28 @@ static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t 
     /* download: [ret (n u64) | out_len (n u32, padded to 8) | packed] */
     const uint64_t head = 8 * n + ((4 * n + 7) & ~7ull);
     const bool one_trip = slots <= HOST_ONE_TRIP;
-    if ((rc = grow(c->d_json, c->d_json_cap, up_bytes))) return rc;
-    if ((rc = grow(c->d_out, c->d_out_cap, slots + 64))) return rc;
-    if ((rc = grow(c->d_pack, c->d_pack_cap, head + slots + 64))) return rc;
-    if ((rc = grow(c->d_pack_off, c->d_po_cap, n + 1))) return rc;
-    if ((rc = grow_pinned(c->h_down, c->h_down_cap, one_trip ? head + slots + 64 : head + 8))) return rc;
+    if ((rc = c->d_json.grow(up_bytes))) return rc;
+    if ((rc = c->d_out.grow(slots + 64))) return rc;
+    if ((rc = c->d_pack.grow(head + slots + 64))) return rc;
+    if ((rc = c->d_pack_off.grow(n + 1))) return rc;
+    if ((rc = c->h_down.grow(one_trip ? head + slots + 64 : head + 8))) return rc;
     const uint64_t *d_in = (const uint64_t *)(void *)c->d_json, *d_oo = d_in + n + 1;
-    HMIn dhm{nullptr, (uint32_t)nhm, nullptr};
+    BatchArgs b; /* the device batch; b.hm: the tables' device copies */
     if (hm) {
-        dhm.tab = nhm ? (const dg_hm_entry *)(const void *)(d_oo + n + 1) : nullptr;
-        dhm.vm = nvm ? (const dg_cb_entry *)(const void *)(d_oo + n + 1 + 2 * n * nhm) : nullptr;
-        dhm.bytes = (const uint8_t *)(const void *)(d_oo + n + 1 + 2 * n * nhm + n * nvm);
+        b.hm.n_hm = (uint32_t)nhm;
+        b.hm.tab = nhm ? (const dg_hm_entry *)(const void *)(d_oo + n + 1) : nullptr;
+        b.hm.vm = nvm ? (const dg_cb_entry *)(const void *)(d_oo + n + 1 + 2 * n * nhm) : nullptr;
+        b.hm.bytes = (const uint8_t *)(const void *)(d_oo + n + 1 + 2 * n * nhm + n * nvm);
     }
     const uint8_t *d_j = c->d_json + 16 * (n + 1) + 8 * hmw;
     uint64_t *d_ret = (uint64_t *)(void *)c->d_pack;
     uint32_t *d_ol = (uint32_t *)(void *)(c->d_pack + 8 * n);
     uint8_t *d_packed = c->d_pack + head;
     HIPCHK(hipMemcpyAsync(c->d_json, c->h_up, up_bytes, hipMemcpyHostToDevice, s));
-    if ((rc = launch(c, d, root, d_j, d_in, n, flags, c->d_out, d_oo, d_ol, d_ret, nullptr, s, max_len,
-                     hm ? &dhm : nullptr)))
-        return rc;
-    if ((rc = pack_scan_nolock(c, c->d_out, d_oo, d_ol, d_ret, n, nullptr, 0, nullptr, 0, d_packed, c->d_pack_off, s)))
-        return rc;
+    b.src = d_j, b.in_off = d_in, b.n = n, b.flags = in.flags, b.max_len = max_len;
+    b.out = c->d_out, b.out_off = d_oo, b.out_len = d_ol, b.ret = d_ret;
+    if ((rc = launch(c, d, root, b, s))) return rc;
+    if ((rc = pack_scan_nolock(c, s, b, nullptr, d_packed, c->d_pack_off))) return rc;
     HIPCHK(hipMemcpyAsync(c->h_down, c->d_pack, one_trip ? head + slots : head, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const uint64_t *hret = (const uint64_t *)(void *)c->h_down;
@@ -931,18 +796,19 @@ static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t 
             if (packed) HIPCHK(hipMemcpy(main_buf.data(), d_packed, packed, hipMemcpyDeviceToHost));
         }
         rhead = 8 * m + ((4 * m + 7) & ~7ull);
-        if ((rc = grow(c->d_json, c->d_json_cap, up.size()))) return rc;
-        if ((rc = grow(c->d_out, c->d_out_cap, so[m] + 64))) return rc;
+        if ((rc = c->d_json.grow(up.size()))) return rc;
+        if ((rc = c->d_out.grow(so[m] + 64))) return rc;
         const uint64_t *r_in = (const uint64_t *)(void *)c->d_json, *r_oo = r_in + m + 1;
         uint64_t *r_ret = (uint64_t *)(void *)c->d_pack; /* rhead <= head: d_pack is large enough */
         uint32_t *r_ol = (uint32_t *)(void *)(c->d_pack + 8 * m);
         HIPCHK(hipMemcpyAsync(c->d_json, up.data(), up.size(), hipMemcpyHostToDevice, s));
-        HMIn rhmd{nhm ? (const dg_hm_entry *)(const void *)(r_oo + m + 1) : nullptr, (uint32_t)nhm,
-                  (const uint8_t *)(const void *)(r_oo + m + 1 + 2 * m * nhm + m * nvm),
-                  nvm ? (const dg_cb_entry *)(const void *)(r_oo + m + 1 + 2 * m * nhm) : nullptr};
-        if ((rc = launch(c, d, root, c->d_json + 16 * (m + 1) + 8 * rhw, r_in, m, flags, c->d_out, r_oo, r_ol, r_ret,
-                         nullptr, s, max_len, hm ? &rhmd : nullptr)))
-            return rc;
+        if (hm)
+            b.hm = HMIn{nhm ? (const dg_hm_entry *)(const void *)(r_oo + m + 1) : nullptr, (uint32_t)nhm,
+                        (const uint8_t *)(const void *)(r_oo + m + 1 + 2 * m * nhm + m * nvm),
+                        nvm ? (const dg_cb_entry *)(const void *)(r_oo + m + 1 + 2 * m * nhm) : nullptr};
+        b.src = c->d_json + 16 * (m + 1) + 8 * rhw, b.in_off = r_in, b.n = m;
+        b.out = c->d_out, b.out_off = r_oo, b.out_len = r_ol, b.ret = r_ret;
+        if ((rc = launch(c, d, root, b, s))) return rc;
         rdown.resize(rhead + so[m]);
         HIPCHK(hipMemcpyAsync(rdown.data(), c->d_pack, rhead, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(rdown.data() + rhead, c->d_out, so[m], hipMemcpyDeviceToHost, s));
@@ -963,8 +829,8 @@ static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t 
         total += olen[i];
         out_off[i + 1] = total;
     }
-    if (out_need) *out_need = total;
-    if (total > out_cap || (!out && total)) return set_err(DG_E_NOMEM, "output needs %llu bytes", (unsigned long long)total);
+    if (o.out_need) *o.out_need = total;
+    if (total > o.out_cap || (!out && total)) return set_err(DG_E_NOMEM, "output needs %llu bytes", (unsigned long long)total);
     if (redo.empty()) {
         /* the packed bytes ARE the output layout */
         if (one_trip) {
@@ -990,11 +856,18 @@ static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t 
     return DG_OK;
 }
 
+static BatchArgs host_batch(const uint8_t *json, const uint64_t *in_off, uint64_t n, uint64_t flags, uint64_t *ret)
+{
+    BatchArgs b;
+    b.src = json, b.in_off = in_off, b.n = n, b.flags = flags, b.ret = ret;
+    return b;
+}
+
 int dg_j2t_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *json, const uint64_t *in_off,
                       uint64_t n, uint64_t flags, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
                       uint64_t *out_need)
 {
-    return batch_host(c, d, root, json, in_off, n, flags, nullptr, 0, out, out_cap, out_off, ret, out_need);
+    return batch_host(c, d, root, host_batch(json, in_off, n, flags, ret), 0, HostOut{out, out_cap, out_off, out_need});
 }
 
 int dg_j2t_batch_host_hm(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *json, const uint64_t *in_off,
@@ -1006,16 +879,18 @@ int dg_j2t_batch_host_hm(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8
     for (uint64_t k = 0; hm_tab && k < n * n_hm; k++)
         if (hm_tab[k].len != DG_HM_ERR && (uint64_t)hm_tab[k].off + hm_tab[k].len > hm_len)
             return set_err(DG_E_INVALID, "HTTP-mapping entry %llu outside the bytes", (unsigned long long)k);
-    HMIn hm{hm_tab, n_hm, hm_bytes};
-    return batch_host(c, d, root, json, in_off, n, flags, hm_tab ? &hm : nullptr, hm_len, out, out_cap, out_off, ret,
-                      out_need);
+    BatchArgs b = host_batch(json, in_off, n, flags, ret);
+    if (hm_tab) b.hm = HMIn{hm_tab, n_hm, hm_bytes};
+    return batch_host(c, d, root, b, hm_len, HostOut{out, out_cap, out_off, out_need});
 }
 
 int dg_j2t_batch_host_cb(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *json, const uint64_t *in_off,
                          uint64_t n, uint64_t flags, const dg_cb_tables *cb, uint8_t *out, uint64_t out_cap,
                          uint64_t *out_off, uint64_t *ret, uint64_t *out_need)
 {
-    if (!cb) return batch_host(c, d, root, json, in_off, n, flags, nullptr, 0, out, out_cap, out_off, ret, out_need);
+    BatchArgs b = host_batch(json, in_off, n, flags, ret);
+    const HostOut o{out, out_cap, out_off, out_need};
+    if (!cb) return batch_host(c, d, root, b, 0, o);
     if ((cb->len && !cb->bytes) || (cb->hm_tab && cb->n_hm && !n)) return set_err(DG_E_INVALID, "bad args");
     for (uint64_t k = 0; cb->hm_tab && k < n * cb->n_hm; k++)
         if (cb->hm_tab[k].len != DG_HM_ERR && (uint64_t)cb->hm_tab[k].off + cb->hm_tab[k].len > cb->len)
@@ -1031,9 +906,8 @@ int dg_j2t_batch_host_cb(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8
             if (at > cb->len) return set_err(DG_E_INVALID, "value-mapping entry %llu outside the bytes", (unsigned long long)i);
         }
     }
-    HMIn hm{cb->hm_tab, cb->hm_tab ? cb->n_hm : 0u, cb->bytes, cb->ans_tab};
-    return batch_host(c, d, root, json, in_off, n, flags, (cb->hm_tab || cb->ans_tab) ? &hm : nullptr, cb->len, out,
-                      out_cap, out_off, ret, out_need);
+    if (cb->hm_tab || cb->ans_tab) b.hm = HMIn{cb->hm_tab, cb->hm_tab ? cb->n_hm : 0u, cb->bytes, cb->ans_tab};
+    return batch_host(c, d, root, b, cb->len, o);
 }
 
 int dg_j2t_do(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *json, size_t len, uint64_t flags,
@@ -1048,103 +922,86 @@ int dg_j2t_do(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *json, s
     return rc;
 }
 
+/* takes no context lock: it launches one kernel and reads only n_cu and the
+ * stream handle, which no other call changes after dg_ctx_create */
 int dg_pack_device(dg_ctx *c, const uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_len, uint64_t n,
                    uint8_t *d_dst, const uint64_t *d_dst_off, void *stream)
 {
     if (!c || (n && (!d_out || !d_out_off || !d_out_len || !d_dst || !d_dst_off))) return set_err(DG_E_INVALID, "bad args");
     if (n == 0) return DG_OK;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)c->stream;
     uint64_t blocks = std::min<uint64_t>((n + 3) / 4, (uint64_t)c->n_cu * 8);
     launch_pack_kernel(dim3((uint32_t)blocks), s, d_out, d_out_off, d_out_len, n, d_dst, d_dst_off);
     HIPCHK(hipGetLastError());
     return DG_OK;
 }
 
-static int pack_scan_nolock(dg_ctx *c, const uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_len,
-                            const uint64_t *d_ret, uint64_t n, const uint8_t *hdr, uint32_t hdr_len, const uint8_t *ftr,
-                            uint32_t ftr_len, uint8_t *d_dst, uint64_t *d_dst_off, hipStream_t s,
-                            const uint64_t *base_in, uint64_t dst_cap, int base_mod16, uint64_t *ret_dst,
-                            uint64_t *cur_out, uint64_t *ovf_out)
+static int pack_scan_nolock(dg_ctx *c, hipStream_t s, const BatchArgs &b, const FrameIn *f, uint8_t *d_dst,
+                            uint64_t *d_dst_off, const PackChain &ch)
 {
-    if (n == 0) {
-        if (ovf_out) HIPCHK(hipMemsetAsync(ovf_out, 0, 8, s));
-        if (base_in && !base_mod16) HIPCHK(hipMemcpyAsync(d_dst_off, base_in, 8, hipMemcpyDefault, s));
+    if (b.n == 0) {
+        if (ch.ovf_out) HIPCHK(hipMemsetAsync(ch.ovf_out, 0, 8, s));
+        if (ch.base_in && !ch.base_mod16) HIPCHK(hipMemcpyAsync(d_dst_off, ch.base_in, 8, hipMemcpyDefault, s));
         else HIPCHK(hipMemsetAsync(d_dst_off, 0, 8, s));
-        if (cur_out) HIPCHK(hipMemcpyAsync(cur_out, d_dst_off, 8, hipMemcpyDefault, s));
+        if (ch.cur_out) HIPCHK(hipMemcpyAsync(ch.cur_out, d_dst_off, 8, hipMemcpyDefault, s));
         return DG_OK;
     }
     Scratch *x;
     int rc = scratch_for(c, s, &x);
     if (rc) return rc;
     MsgFrame fr{};
-    fr.ret = d_ret; /* failed messages pack as nothing */
-    fr.base_in = base_in;
-    fr.dst_cap = dst_cap;
-    fr.base_mod16 = base_mod16 ? 1u : 0u;
-    fr.phase_add = (uint32_t)(base_mod16 >> 1) & 15; /* dg_i_convert_pack: 1 | phase << 1 */
-    fr.ret_dst = ret_dst;
-    fr.cur_out = cur_out;
-    fr.ovf_out = d_ret ? ovf_out : nullptr;
-    if (hdr) {
+    fr.ret = b.ret; /* failed messages pack as nothing */
+    fr.base_in = ch.base_in;
+    fr.dst_cap = ch.dst_cap;
+    fr.base_mod16 = ch.base_mod16 ? 1u : 0u;
+    fr.phase_add = (uint32_t)(ch.base_mod16 >> 1) & 15; /* PackChain: 1 | phase << 1 */
+    fr.ret_dst = ch.ret_dst;
+    fr.cur_out = ch.cur_out;
+    fr.ovf_out = b.ret ? ch.ovf_out : nullptr;
+    if (f) {
         /* header at 0, footer 8-aligned after it; both followed by >= 16 readable bytes */
-        const uint32_t fo = (hdr_len + 7) & ~7u;
-        std::vector<uint8_t> tmp(fo + ftr_len + 16, 0);
-        memcpy(tmp.data(), hdr, hdr_len);
-        if (ftr_len) memcpy(tmp.data() + fo, ftr, ftr_len);
+        const uint32_t fo = (f->hdr_len + 7) & ~7u;
+        std::vector<uint8_t> tmp(fo + f->ftr_len + 16, 0);
+        memcpy(tmp.data(), f->hdr, f->hdr_len);
+        if (f->ftr_len) memcpy(tmp.data() + fo, f->ftr, f->ftr_len);
         if (tmp != x->frame) {
             /* a new header/footer (a new method): wait until the scratch's
              * last launch is done reading the old one, then upload */
-            if (x->used) HIPCHK(hipEventSynchronize(x->done));
+            HIPCHK(x->wait_host());
             HIPCHK(hipMemcpy(x->d_frame, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
             x->frame = tmp;
         }
         fr.hdr = x->d_frame;
-        fr.hdr_len = hdr_len;
+        fr.hdr_len = f->hdr_len;
         fr.ftr = x->d_frame + fo;
-        fr.ftr_len = ftr_len;
+        fr.ftr_len = f->ftr_len;
     }
     /* every block must be resident at once (they wait for each other): at
      * most one block per CU */
-    const uint64_t G = std::min<uint64_t>((n + 255) / 256, (uint64_t)c->n_cu);
-    launch_pack_scan_kernel(dim3((uint32_t)G), s, d_out, d_out_off, d_out_len, n, d_dst, d_dst_off, x->d_sums,
-                            x->d_counts + 6, fr);
+    const uint64_t G = std::min<uint64_t>((b.n + 255) / 256, (uint64_t)c->n_cu);
+    launch_pack_scan_kernel(dim3((uint32_t)G), s, b.out, b.out_off, b.out_len, b.n, d_dst, d_dst_off, x->sums,
+                            x->counts + CNT_PACK, fr);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) (void)hipMemsetAsync(x->d_counts + 6, 0, 8, s);
-    HIPCHK(hipEventRecord(x->done, s));
-    x->used = true;
-    x->last = s;
+    if (e != hipSuccess) (void)hipMemsetAsync(x->counts + CNT_PACK, 0, 8, s);
+    HIPCHK(x->publish(s));
     if (e != hipSuccess) return set_err(DG_E_HIP, "pack scan launch: %s", hipGetErrorString(e));
     return DG_OK;
-}
-
-static int pack_scan(dg_ctx *c, const uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_len,
-                     const uint64_t *d_ret, uint64_t n, const uint8_t *hdr, uint32_t hdr_len, const uint8_t *ftr,
-                     uint32_t ftr_len, uint8_t *d_dst, uint64_t *d_dst_off, void *stream)
-{
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return pack_scan_nolock(c, d_out, d_out_off, d_out_len, d_ret, n, hdr, hdr_len, ftr, ftr_len, d_dst, d_dst_off, s);
 }
 
 }  // extern "C"
 
 /* conversion + packing of one batch on stream s (failed and overflowed
  * messages pack as nothing), for the pipelined host paths (j2t_pipe.hip) */
-int dg_i_convert_pack(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_json, const uint64_t *d_in_off,
-                      uint64_t n, uint64_t flags, uint8_t *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
-                      uint64_t *d_ret, uint8_t *d_packed, uint64_t *d_pack_off, hipStream_t s, uint64_t max_len,
-                      const uint64_t *base_in, uint64_t dst_cap, hipEvent_t pack_after, int base_mod16,
-                      uint64_t *ret_dst, uint64_t *cur_out, uint64_t *ovf_out)
+int dg_i_convert_pack(dg_ctx *c, const dg_desc *d, uint32_t root, const BatchArgs &b, uint8_t *packed,
+                      uint64_t *pack_off, hipStream_t s, const PackChain &ch)
 {
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    int rc = launch(c, d, root, d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, nullptr, s, max_len);
+    Entry g(c, true);
+    if (g.rc) return g.rc;
+    int rc = launch(c, d, root, b, s);
     if (rc) return rc;
-    if (pack_after) HIPCHK(hipStreamWaitEvent(s, pack_after, 0));
-    return pack_scan_nolock(c, d_out, d_out_off, d_out_len, d_ret, n, nullptr, 0, nullptr, 0, d_packed, d_pack_off, s,
-                            base_in, dst_cap, base_mod16, ret_dst, cur_out, ovf_out);
+    if (ch.pack_after) HIPCHK(hipStreamWaitEvent(s, ch.pack_after, 0));
+    return pack_scan_nolock(c, s, b, nullptr, packed, pack_off, ch);
 }
 
 extern "C" {
@@ -1152,41 +1009,42 @@ extern "C" {
 int dg_pack_device_scan(dg_ctx *c, const uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_len,
                         uint64_t n, uint8_t *d_dst, uint64_t *d_dst_off, void *stream)
 {
-    if (!c || !d_dst_off || (n && (!d_out || !d_out_off || !d_out_len || !d_dst))) return set_err(DG_E_INVALID, "bad args");
-    return pack_scan(c, d_out, d_out_off, d_out_len, nullptr, n, nullptr, 0, nullptr, 0, d_dst, d_dst_off, stream);
+    Entry g(c, c && d_dst_off && !(n && (!d_out || !d_out_off || !d_out_len || !d_dst)), stream);
+    if (g.rc) return g.rc;
+    BatchArgs b;
+    b.out = (uint8_t *)d_out, b.out_off = d_out_off, b.out_len = (uint32_t *)d_out_len, b.n = n;
+    return pack_scan_nolock(c, g.s, b, nullptr, d_dst, d_dst_off);
 }
 
 int dg_pack_device_framed(dg_ctx *c, const uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_len,
                           const uint64_t *d_ret, uint64_t n, const uint8_t *hdr, uint32_t hdr_len, const uint8_t *ftr,
                           uint32_t ftr_len, uint8_t *d_dst, uint64_t *d_dst_off, void *stream)
 {
-    if (!c || !d_dst_off || !hdr || (ftr_len && !ftr) || ((hdr_len + 7) & ~7u) + ftr_len + 16 > FRAME_CAP ||
-        (n && (!d_out || !d_out_off || !d_out_len || !d_ret || !d_dst)))
-        return set_err(DG_E_INVALID, "bad args");
-    return pack_scan(c, d_out, d_out_off, d_out_len, d_ret, n, hdr, hdr_len, ftr, ftr_len, d_dst, d_dst_off, stream);
+    Entry g(c, c && d_dst_off && hdr && (!ftr_len || ftr) && ((hdr_len + 7) & ~7u) + ftr_len + 16 <= FRAME_CAP &&
+                   !(n && (!d_out || !d_out_off || !d_out_len || !d_ret || !d_dst)), stream);
+    if (g.rc) return g.rc;
+    BatchArgs b; /* the packing only reads these */
+    b.out = (uint8_t *)d_out, b.out_off = d_out_off, b.out_len = (uint32_t *)d_out_len, b.ret = (uint64_t *)d_ret, b.n = n;
+    const FrameIn f{hdr, ftr, hdr_len, ftr_len};
+    return pack_scan_nolock(c, g.s, b, &f, d_dst, d_dst_off);
 }
 
 int dg_bench_device(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_json, const uint64_t *d_in_off,
                     uint64_t n, uint64_t flags, uint8_t *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
                     uint64_t *d_ret, int iters, float *ms)
 {
-    if (!c || !d || iters < 1 || !ms) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, c->stream));
-    for (int k = 0; k < iters; k++) {
-        int rc = launch(c, d, root, d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, c->d_pending,
-                        c->stream);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(e1, c->stream));
+    Entry g(c, c && d && iters >= 1 && ms);
+    if (g.rc) return g.rc;
+    Event e0, e1;
+    HIPCHK(e0.create());
+    HIPCHK(e1.create());
+    HIPCHK(hipEventRecord(e0, g.s));
+    const BatchArgs b{d_json, d_in_off, n, flags, d_out, d_out_off, d_out_len, d_ret, c->d_pending};
+    for (int k = 0; k < iters; k++)
+        if (int rc = launch(c, d, root, b, g.s)) return rc;
+    HIPCHK(hipEventRecord(e1, g.s));
     HIPCHK(hipEventSynchronize(e1));
     HIPCHK(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return DG_OK;
 }
 

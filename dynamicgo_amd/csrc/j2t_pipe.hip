@@ -185,16 +185,15 @@ __global__ __launch_bounds__(256) void pipe_copy_out_kernel(const uint8_t *src, 
 /* device buffers of one batch in flight, grown on demand while idle:
  * [in_off | out_off] offsets, JSON, slots, out_len, ret */
 struct DevBuf {
-    uint64_t *d_off = nullptr; uint64_t off_cap = 0;   /* in_off (n+1) | out_off (n+1) */
-    uint8_t *d_json = nullptr; uint64_t json_cap = 0;
-    uint8_t *d_out = nullptr; uint64_t out_cap = 0;
-    uint32_t *d_ol = nullptr; uint64_t ol_cap = 0;
-    uint64_t *d_ret = nullptr; uint64_t ret_cap = 0;
+    DevArr<uint64_t> d_off; /* in_off (n+1) | out_off (n+1) */
+    DevArr<uint8_t> d_json, d_out;
+    DevArr<uint32_t> d_ol;
+    DevArr<uint64_t> d_ret;
 
     bool fits(uint64_t n, uint64_t b) const
     {
-        return off_cap >= 2 * (n + 1) && json_cap >= b + 64 + 16 && out_cap >= slot_off(b, n) + 64 &&
-               ol_cap >= n + 1 && ret_cap >= n + 1;
+        return d_off.cap >= 2 * (n + 1) && d_json.cap >= b + 64 + 16 && d_out.cap >= slot_off(b, n) + 64 &&
+               d_ol.cap >= n + 1 && d_ret.cap >= n + 1;
     }
     /* callers make sure no launch still uses the buffers when they grow.
      * Growth is sized for twice the batch that needed it (every buffer at
@@ -208,40 +207,19 @@ struct DevBuf {
             n = 2 * n + 64;
             b = 2 * b + 4096;
         }
-        if ((rc = grow(d_off, off_cap, 2 * (n + 1)))) return rc;
-        if ((rc = grow(d_json, json_cap, b + 64 + 16))) return rc;
-        if ((rc = grow(d_out, out_cap, slot_off(b, n) + 64))) return rc;
-        if ((rc = grow(d_ol, ol_cap, n + 1))) return rc;
-        if ((rc = grow(d_ret, ret_cap, n + 1))) return rc;
-        return DG_OK;
+        if ((rc = d_off.grow(2 * (n + 1)))) return rc;
+        if ((rc = d_json.grow(b + 64 + 16))) return rc;
+        if ((rc = d_out.grow(slot_off(b, n) + 64))) return rc;
+        if ((rc = d_ol.grow(n + 1))) return rc;
+        return d_ret.grow(n + 1);
     }
-    void release()
+    /* the batch of n messages whose offsets are at in_off / out_off, JSON at json */
+    BatchArgs batch(const uint8_t *json, const uint64_t *in_off, const uint64_t *out_off, uint64_t n) const
     {
-        (void)hipFree(d_off);
-        (void)hipFree(d_json);
-        (void)hipFree(d_out);
-        (void)hipFree(d_ol);
-        (void)hipFree(d_ret);
-        d_off = d_ret = nullptr;
-        d_json = d_out = nullptr;
-        d_ol = nullptr;
-        off_cap = json_cap = out_cap = ol_cap = ret_cap = 0;
-    }
-    /* convert + pack n messages whose offsets are at in_off / out_off, JSON
-     * at json. The packing writes straight into pinned host memory: bytes at
-     * h_dst + h_dst_off[i] (positions from *base_in when chained, nothing
-     * past dst_cap), after the event pack_after if set; then ret is
-     * downloaded to h_ret and ev recorded. */
-    int convert(dg_ctx *c, const dg_desc *d, uint32_t root, uint64_t flags, uint64_t n, const uint8_t *json,
-                const uint64_t *in_off, const uint64_t *out_off, uint64_t max_len, hipStream_t s, uint64_t *h_ret,
-                uint8_t *h_dst, uint64_t *h_dst_off, const uint64_t *base_in, uint64_t dst_cap, hipEvent_t pack_after,
-                hipEvent_t ev)
-    {
-        int rc = dg_i_convert_pack(c, d, root, json, in_off, n, flags, d_out, out_off, d_ol, d_ret, h_dst, h_dst_off,
-                                   s, max_len, base_in, dst_cap, pack_after, 0, h_ret);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(ev, s));
-        return DG_OK;
+        BatchArgs b;
+        b.src = json, b.in_off = in_off, b.n = n;
+        b.out = d_out, b.out_off = out_off, b.out_len = d_ol, b.ret = d_ret;
+        return b;
     }
 };
 
@@ -271,13 +249,19 @@ struct alignas(128) Sub {
     std::atomic<uint32_t> n{0};    /* messages committed */
     uint64_t bytes = 0;            /* JSON bytes committed (owner-written) */
     uint64_t maxlen = 0;           /* its longest message (owner-written) */
-    uint8_t *h = nullptr;          /* pinned: [ends (cap_n u64) | JSON (cap_b + 64)] */
+    PinArr<uint8_t> h;             /* pinned: [ends (cap_n u64) | JSON (cap_b + 64)] */
     uint64_t gbase = 0;            /* set at the seal: its first global index */
     std::atomic<uint32_t> left{0}; /* results not yet taken */
-    uint64_t *ends() const { return (uint64_t *)(void *)h; }
+    uint64_t *ends() const { return (uint64_t *)(void *)h.p; }
 };
 
+/* Destruction: the host waits for the batch's stream, then the members go in
+ * reverse order -- buffers first, the events and the stream (declared first)
+ * last. The context's scratches used on the stream go before it does
+ * (dg_agg_destroy). */
 struct Batch {
+    Stream s;
+    Event ev_hdr, ev_done;
     Sub sub[AGG_SLOTS];
     std::atomic<uint64_t> t_first{0}; /* ns timestamp of its first message (0: none yet) */
     std::atomic<uint32_t> seal_req{0};
@@ -288,18 +272,20 @@ struct Batch {
     uint64_t t_launched = 0;
     uint64_t n = 0, bytes = 0;
     int rc = DG_OK;
-    hipStream_t s = nullptr;
-    hipEvent_t ev_hdr = nullptr, ev_done = nullptr;
     DevBuf dv;
-    uint8_t *h_hdr = nullptr; uint64_t h_hdr_cap = 0;       /* pinned [ret | pack_off] */
-    uint8_t *h_packed = nullptr; uint64_t h_packed_cap = 0; /* pinned packed Thrift */
-    SubRef *h_tab = nullptr;                                /* pinned sub-batch table */
-    SubRef *d_tab = nullptr;
+    PinArr<uint8_t> h_hdr;    /* pinned [ret | pack_off] */
+    PinArr<uint8_t> h_packed; /* pinned packed Thrift */
+    PinArr<SubRef> h_tab;     /* pinned sub-batch table */
+    DevArr<SubRef> d_tab;
     std::atomic<uint64_t> done_g{0};  /* last generation whose results are readable */
     std::mutex mu;
     std::condition_variable cv;
     bool free_ = true;                /* under the aggregator's mu */
-    const uint64_t *ret() const { return (const uint64_t *)(const void *)h_hdr; }
+    const uint64_t *ret() const { return (const uint64_t *)(const void *)h_hdr.p; }
+    ~Batch()
+    {
+        if (s) (void)hipStreamSynchronize(s);
+    }
     const uint64_t *pack_off() const { return ret() + n; }
 };
 
@@ -454,10 +440,7 @@ int dg_agg::slot(bool &shared)
             bool ok = true;
             (void)hipSetDevice(ctx->device);
             for (int r = 0; r < ring && ok; r++) {
-                uint64_t cap = 0;
-                uint8_t *h = nullptr;
-                ok = grow_pinned(h, cap, 8 * cap_n + cap_b + 64) == DG_OK;
-                b[r].sub[j].h = h;
+                ok = b[r].sub[j].h.grow(8 * cap_n + cap_b + 64) == DG_OK;
             }
             if (!ok) {
                 s = -1;
@@ -470,10 +453,7 @@ int dg_agg::slot(bool &shared)
         bool ok = true;
         (void)hipSetDevice(ctx->device);
         for (int k = 0; k < ring && ok; k++) {
-            uint64_t cap = 0;
-            uint8_t *h = nullptr;
-            ok = grow_pinned(h, cap, 8 * cap_n + cap_b + 64) == DG_OK;
-            b[k].sub[s].h = h;
+            ok = b[k].sub[s].h.grow(8 * cap_n + cap_b + 64) == DG_OK;
         }
         ready[s].store(ok ? 1 : 2, std::memory_order_release);
         if (!ok) s = -1;
@@ -519,9 +499,9 @@ int dg_agg::launch(Batch *x)
     const bool exact = slot_off(Bx, Nx) * (uint64_t)ring <= exact_total.load(std::memory_order_relaxed);
     const uint64_t Ng = exact ? Nx : 2 * N + 64, Bg = exact ? Bx : 2 * B + 4096;
     if ((rc = x->dv.reserve(exact ? Nx : N, exact ? Bx : B, exact))) return rc;
-    if (x->h_hdr_cap < 16 * N + 8 && (rc = grow_pinned(x->h_hdr, x->h_hdr_cap, 16 * Ng + 8))) return rc;
-    if (x->h_packed_cap < slot_off(B, N) + 64 && /* >= any packed size */
-        (rc = grow_pinned(x->h_packed, x->h_packed_cap, slot_off(Bg, Ng) + 64)))
+    if (x->h_hdr.cap < 16 * N + 8 && (rc = x->h_hdr.grow(16 * Ng + 8))) return rc;
+    if (x->h_packed.cap < slot_off(B, N) + 64 && /* >= any packed size */
+        (rc = x->h_packed.grow(slot_off(Bg, Ng) + 64)))
         return rc;
     /* the parts' longest message (the callers track it) picks the kernels */
     uint64_t max_len = 1;
@@ -538,9 +518,15 @@ int dg_agg::launch(Batch *x)
                        x->dv.d_json, N, B, d_in, d_oo);
     HIPCHK(hipGetLastError());
     const uint64_t l3 = now_ns();
-    uint64_t *h_ret = (uint64_t *)(void *)x->h_hdr;
-    rc = x->dv.convert(ctx, desc, root, flags, N, x->dv.d_json, d_in, d_oo, max_len, x->s, h_ret, x->h_packed,
-                       h_ret + N, nullptr, 0, nullptr, x->ev_hdr);
+    /* convert + pack; the packing writes straight into pinned host memory
+     * (bytes at h_packed + pack_off[i]), then ret is downloaded behind it */
+    uint64_t *h_ret = (uint64_t *)(void *)x->h_hdr.p;
+    BatchArgs cb = x->dv.batch(x->dv.d_json, d_in, d_oo, N);
+    cb.flags = flags, cb.max_len = max_len;
+    PackChain ch;
+    ch.ret_dst = h_ret;
+    rc = dg_i_convert_pack(ctx, desc, root, cb, x->h_packed, h_ret + N, x->s, ch);
+    if (!rc && hipEventRecord(x->ev_hdr, x->s) != hipSuccess) rc = set_err(DG_E_HIP, "hipEventRecord(ev_hdr)");
     const uint64_t l4 = now_ns();
     prof[13].fetch_add(l2 - l1, std::memory_order_relaxed);
     prof[14].fetch_add(l3 - l2, std::memory_order_relaxed);
@@ -705,58 +691,30 @@ void dg_agg::run_completer()
 
 /* ---------------- the pipelined host batch ---------------- */
 
-namespace {
-
 constexpr int PIPE_BUFS = 3;
 
-/* one chunk in flight: a stream, events, device buffers, pinned header */
+/* one chunk in flight: a stream, events, device buffers. Destruction: the
+ * host waits for the stream, then buffers, events and the stream go */
 struct PipeBuf {
-    hipStream_t s = nullptr;
-    hipEvent_t ev_hdr = nullptr, ev_done = nullptr;
+    Stream s;
+    Event ev_hdr, ev_done;
     DevBuf dv;
-    uint8_t *d_packed = nullptr; uint64_t packed_cap = 0; /* [pack_off (n+1) | packed (16-aligned)] */
+    DevArr<uint8_t> d_packed; /* [pack_off (n+1) | packed (16-aligned)] */
     int init(int dev)
     {
         HIPCHK(hipSetDevice(dev));
-        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&ev_hdr, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
+        HIPCHK(s.create(hipStreamNonBlocking));
+        HIPCHK(ev_hdr.create(hipEventDisableTiming));
+        HIPCHK(ev_done.create(hipEventDisableTiming));
         return DG_OK;
     }
-    void release()
+    ~PipeBuf()
     {
         if (s) (void)hipStreamSynchronize(s);
-        dv.release();
-        (void)hipFree(d_packed);
-        d_packed = nullptr;
-        packed_cap = 0;
-        if (ev_hdr) (void)hipEventDestroy(ev_hdr);
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        if (s) (void)hipStreamDestroy(s);
-        s = nullptr;
     }
 };
 
-}  // namespace
-
-void dg_i_pipe_free(dg_ctx *c)
-{
-    for (void *q : c->pipe) {
-        ((PipeBuf *)q)->release();
-        delete (PipeBuf *)q;
-    }
-    c->pipe.clear();
-    (void)hipFree(c->d_pipe_cur);
-    c->d_pipe_cur = nullptr;
-    c->pipe_cur_cap = 0;
-    (void)hipHostFree(c->h_pipe_ovf);
-    c->h_pipe_ovf = nullptr;
-    c->h_pipe_ovf_cap = 0;
-    (void)hipHostFree(c->h_pipe_out);
-    (void)hipHostFree(c->h_pipe_aux);
-    c->h_pipe_out = c->h_pipe_aux = nullptr;
-    c->h_pipe_out_cap = c->h_pipe_aux_cap = 0;
-}
+void PipeBufDelete::operator()(PipeBuf *p) const { delete p; }
 
 extern "C" {
 
@@ -781,12 +739,11 @@ int dg_agg_create2(dg_ctx *ctx, const dg_desc *desc, uint32_t root_type, uint64_
     (void)hipSetDevice(ctx->device);
     for (int k = 0; k < a->ring && rc == DG_OK; k++) {
         Batch &x = a->b[k];
-        hipError_t e = hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&x.ev_hdr, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&x.ev_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&x.h_tab, sizeof(SubRef) * AGG_SLOTS, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc(&x.d_tab, sizeof(SubRef) * AGG_SLOTS);
+        hipError_t e = x.s.create(hipStreamNonBlocking);
+        if (e == hipSuccess) e = x.ev_hdr.create(hipEventDisableTiming);
+        if (e == hipSuccess) e = x.ev_done.create(hipEventDisableTiming);
         if (e != hipSuccess) rc = set_err(DG_E_HIP, "aggregator setup: %s", hipGetErrorString(e));
+        else if (!(rc = x.h_tab.alloc(AGG_SLOTS))) rc = x.d_tab.alloc(AGG_SLOTS);
     }
     if (rc) {
         dg_agg_destroy(a);
@@ -991,20 +948,7 @@ void dg_agg_destroy(dg_agg *a)
         for (int k = 0; k < a->ring; k++)
             if (a->b[k].s) ss.push_back(a->b[k].s);
         dg_i_scratch_release(a->ctx, ss.data(), (int)ss.size());
-        for (int k = 0; k < a->ring; k++) {
-            Batch &x = a->b[k];
-            if (x.s) (void)hipStreamSynchronize(x.s);
-            for (Sub &u : x.sub) (void)hipHostFree(u.h);
-            x.dv.release();
-            (void)hipFree(x.d_tab);
-            (void)hipHostFree(x.h_tab);
-            (void)hipHostFree(x.h_hdr);
-            (void)hipHostFree(x.h_packed);
-            if (x.ev_hdr) (void)hipEventDestroy(x.ev_hdr);
-            if (x.ev_done) (void)hipEventDestroy(x.ev_done);
-            if (x.s) (void)hipStreamDestroy(x.s);
-        }
-        delete[] a->b;
+        delete[] a->b; /* ~Batch */
     }
     delete a;
 }
@@ -1048,10 +992,9 @@ int dg_j2t_pipeline_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8
     std::lock_guard<std::mutex> pg(c->pipe_mu);
     HIPCHK(hipSetDevice(c->device));
     while (c->pipe.size() < (size_t)PIPE_BUFS) {
-        PipeBuf *q = new PipeBuf();
-        c->pipe.push_back(q);
-        int rc = q->init(c->device);
-        if (rc) return rc;
+        std::unique_ptr<PipeBuf, PipeBufDelete> q(new PipeBuf());
+        if (int rc = q->init(c->device)) return rc;
+        c->pipe.push_back(std::move(q));
     }
     const int nb = (int)std::min<uint32_t>(PIPE_BUFS, chunks);
     /* where the results go: the caller's buffers if pinned, else staging */
@@ -1062,28 +1005,24 @@ int dg_j2t_pipeline_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8
     uint64_t *p_off = (uint64_t *)dv_off, *p_ret = (uint64_t *)dv_ret;
     if (!direct) {
         int rc;
-        if ((rc = grow_pinned(c->h_pipe_out, c->h_pipe_out_cap, out_cap + 64))) return rc;
-        if ((rc = grow_pinned(c->h_pipe_aux, c->h_pipe_aux_cap, 16 * n + 16))) return rc;
+        if ((rc = c->h_pipe_out.grow(out_cap + 64))) return rc;
+        if ((rc = c->h_pipe_aux.grow(16 * n + 16))) return rc;
         p_out = c->h_pipe_out;
-        p_off = (uint64_t *)(void *)c->h_pipe_aux;
+        p_off = (uint64_t *)(void *)c->h_pipe_aux.p;
         p_ret = p_off + n + 1;
     }
     const uint32_t phase = (uint32_t)((uintptr_t)p_out & 15);
     /* chunk k's start in out, written by chunk k-1's copy-out: the next
      * chunk's kernels read it from device memory (one read per block), not
      * over the link */
-    if (c->pipe_cur_cap < chunks + 1) {
+    if (c->d_pipe_cur.cap < chunks + 1) {
         HIPCHK(hipDeviceSynchronize()); /* no chain of an earlier call still reads it */
-        int rc;
-        if ((rc = grow(c->d_pipe_cur, c->pipe_cur_cap, (uint64_t)chunks + 1))) return rc;
+        if (int rc = c->d_pipe_cur.grow((uint64_t)chunks + 1)) return rc;
     }
     /* each chunk's packing counts its overflowed slots here, so the host
      * scans the status words (pinned: slow CPU reads) only when one did */
-    {
-        int rc;
-        if ((rc = grow_pinned(c->h_pipe_ovf, c->h_pipe_ovf_cap, 8ull * chunks))) return rc;
-    }
-    uint64_t *h_ovf = (uint64_t *)(void *)c->h_pipe_ovf;
+    if (int rc = c->h_pipe_ovf.grow(8ull * chunks)) return rc;
+    uint64_t *h_ovf = (uint64_t *)(void *)c->h_pipe_ovf.p;
     /* zero copy: when the JSON arena (with the 16 readable bytes past its end
      * the kernels may touch) and the offsets are pinned, the kernels read
      * them over the link themselves -- no hipMemcpyAsync per chunk, and the
@@ -1104,7 +1043,7 @@ int dg_j2t_pipeline_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8
         fprintf(stderr, "dg_j2t_pipeline_host: n=%llu chunks=%u direct=%d zero_copy=%d staged=%d\n",
                 (unsigned long long)n, chunks, (int)direct, (int)zc, (int)staged);
     for (uint32_t k = 0; k < chunks; k++) {
-        PipeBuf &p = *(PipeBuf *)c->pipe[k % nb];
+        PipeBuf &p = *c->pipe[k % nb];
         const uint64_t a = cb[k], m = cb[k + 1] - a, base = in_off[a], jb = base & ~15ull;
         /* the longest message picks the kernels; unknown (0) when the
          * offsets are pinned (read in place or uploaded): CPU reads of pinned
@@ -1118,11 +1057,11 @@ int dg_j2t_pipeline_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8
         const uint64_t span = in_off[a + m] - jb;
         const uint64_t pk = 8 * (m + 1) + 16 + slot_off(span, m) + 64; /* pack_off + phase + packed */
         int rc;
-        if (!p.dv.fits(m, span) || (staged && p.packed_cap < pk)) HIPCHK(hipStreamSynchronize(p.s)); /* free to grow */
+        if (!p.dv.fits(m, span) || (staged && p.d_packed.cap < pk)) HIPCHK(hipStreamSynchronize(p.s)); /* free to grow */
         if ((rc = p.dv.reserve(m, span))) return rc;
-        if (staged && (rc = grow(p.d_packed, p.packed_cap, pk))) return rc;
+        if (staged && (rc = p.d_packed.grow(pk))) return rc;
         uint64_t *d_in = p.dv.d_off, *d_oo = d_in + m + 1;
-        uint64_t *d_po = (uint64_t *)(void *)p.d_packed;
+        uint64_t *d_po = (uint64_t *)(void *)p.d_packed.p;
         uint8_t *d_pk = p.d_packed + ((8 * (m + 1) + 15) & ~15ull);
         const uint8_t *j_base; /* the JSON the kernels read, in_off-relative */
         const uint64_t *j_in;
@@ -1141,24 +1080,24 @@ int dg_j2t_pipeline_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8
         }
         HIPCHK(hipGetLastError());
         /* the packing needs the previous chunk's end (written by its pack or copy-out) */
-        PipeBuf *prev = k ? (PipeBuf *)c->pipe[(k - 1) % nb] : nullptr;
+        PipeBuf *prev = k ? c->pipe[(k - 1) % nb].get() : nullptr;
         const uint64_t *base_ptr = k ? c->d_pipe_cur + k : nullptr;
+        BatchArgs b = p.dv.batch(j_base, j_in, d_oo, m);
+        b.flags = flags, b.max_len = max_len;
+        PackChain ch;
+        ch.base_in = base_ptr ? base_ptr : c->d_zero.p;
+        ch.pack_after = prev ? (hipEvent_t)prev->ev_hdr : nullptr;
+        ch.ovf_out = h_ovf + k;
         if (!staged) {
             /* the packing's coalesced stores are the download: straight into
              * out / out_off / ret (pinned), from the previous chunk's end */
-            if ((rc = dg_i_convert_pack(c, d, root, j_base, j_in, m, flags, p.dv.d_out, d_oo, p.dv.d_ol, p.dv.d_ret,
-                                        p_out, p_off + a, p.s, max_len, base_ptr ? base_ptr : c->d_zero, out_cap,
-                                        prev ? prev->ev_hdr : nullptr, 0, p_ret + a, c->d_pipe_cur + k + 1,
-                                        h_ovf + k)))
-                return rc;
+            ch.dst_cap = out_cap, ch.ret_dst = p_ret + a, ch.cur_out = c->d_pipe_cur + k + 1;
+            if ((rc = dg_i_convert_pack(c, d, root, b, p_out, p_off + a, p.s, ch))) return rc;
             HIPCHK(hipEventRecord(p.ev_hdr, p.s));
             continue;
         }
-        if ((rc = dg_i_convert_pack(c, d, root, j_base, j_in, m, flags, p.dv.d_out, d_oo, p.dv.d_ol,
-                                    p.dv.d_ret, d_pk, d_po, p.s, max_len, base_ptr ? base_ptr : c->d_zero, 0,
-                                    prev ? prev->ev_hdr : nullptr, 1 | (int)(phase << 1), nullptr, nullptr,
-                                    h_ovf + k)))
-            return rc;
+        ch.base_mod16 = 1 | (int)(phase << 1);
+        if ((rc = dg_i_convert_pack(c, d, root, b, d_pk, d_po, p.s, ch))) return rc;
         const uint32_t cg = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((span / 16 + 255) / 256, (m + 256) / 256),
                                                          (uint64_t)c->n_cu * 4);
         hipLaunchKernelGGL(pipe_copy_out_kernel, dim3(cg), dim3(256), 0, p.s, d_pk, d_po, m, p.dv.d_ret, p_out,
@@ -1166,7 +1105,7 @@ int dg_j2t_pipeline_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(p.ev_hdr, p.s));
     }
-    for (int i = 0; i < nb; i++) HIPCHK(hipStreamSynchronize(((PipeBuf *)c->pipe[i])->s));
+    for (int i = 0; i < nb; i++) HIPCHK(hipStreamSynchronize(c->pipe[i]->s));
     /* the host's view of the offsets (a hipHostRegister'd buffer's device
      * alias need not equal its host address) */
     const uint64_t cursor = direct ? out_off[n] : p_off[n];

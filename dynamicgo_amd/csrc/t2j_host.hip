@@ -31,11 +31,9 @@ static uint32_t t2j_spread(const dg_ctx *c, uint64_t max_len)
  * what the lane passes queued (it also zeroes the counter set the previous
  * launch used); the scratch's `done`
  * event after. */
-static int t2j_launch(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *src, const uint64_t *in_off,
-                      uint64_t n, uint64_t opts, uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
-                      uint64_t *ret, hipStream_t s, uint64_t max_len, uint64_t *aux = nullptr,
-                      const dg_cb_entry *ans = nullptr, const uint8_t *ans_bytes = nullptr)
+static int t2j_launch(dg_ctx *c, const dg_desc *d, uint32_t root, const BatchArgs &b, hipStream_t s)
 {
+    const uint64_t n = b.n, opts = b.flags;
     if (n == 0) return DG_OK;
     if (!d->d_side) return set_err(DG_E_DESC, "descriptor has no t2j side table (dg_desc_attach_t2j)");
     if (root >= d->hdr.n_types) return set_err(DG_E_INVALID, "root type %u out of range", root);
@@ -43,67 +41,60 @@ static int t2j_launch(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t 
     Scratch *x;
     int rc = scratch_for(c, s, &x);
     if (rc) return rc;
-    if ((rc = grow_x(x, x->t2j_list, x->t2j_list_cap, n))) return rc;
-    if (!c->ws_t2j) {
-        HIPCHK(hipMalloc(&c->ws_t2j, T2J_DEEP_WS));
-        /* ordering only (the next deep pass on another stream): no system-scope fence */
-        HIPCHK(hipEventCreateWithFlags(&c->ws_t2j_done, hipEventDisableTiming | hipEventDisableSystemFence));
-    }
+    if ((rc = x->grow(x->t2j_list, n))) return rc;
+    if (!c->t2j_deep.ws && (rc = c->t2j_deep.ws.alloc(T2J_DEEP_WS))) return rc;
     const uint64_t wmin = (uint64_t)c->knobs.t2j_wave_min;
     /* the root-level Go-side options run on the lane kernel only */
     const bool wave = !(opts & (DG_T2J_CONVERT_EXC | DG_T2J_SKIP_RESP_BASE | DG_T2J_HM)) && wmin > 0 && d->hdr.total_len <= 16384 && d->hdr.n_fields <= 1024 && /* T2W_FX */
                       d->hdr.n_types < 4096 && /* a token's type index */
-                      d->side_len <= 12288 /* T2W_SIDE */ && (max_len == 0 || max_len > wmin);
+                      d->side_len <= 12288 /* T2W_SIDE */ && (b.max_len == 0 || b.max_len > wmin);
     if (wave) {
-        if ((rc = grow_x(x, x->t2j_big, x->t2j_big_cap, n))) return rc;
-        if ((rc = grow_x(x, x->t2j_bail, x->t2j_bail_cap, n))) return rc;
-        if (!c->ws_t2w) HIPCHK(hipMalloc(&c->ws_t2w, t2j_wave_ws_bytes((uint32_t)c->n_cu * T2W_BPC)));
+        if ((rc = x->grow(x->t2j_big, n))) return rc;
+        if ((rc = x->grow(x->t2j_bail, n))) return rc;
+        if (!c->t2j_tok.ws && (rc = c->t2j_tok.ws.alloc(t2j_wave_ws_bytes((uint32_t)c->n_cu * T2W_BPC)))) return rc;
     }
     /* overlapped form: the wave kernel (and its bails' list pass) on the
      * scratch's second stream, beside the lane pass over the short ones, so
      * the lane pass fills the CUs the persistent wave grid leaves idle */
     const bool ovl = wave && c->knobs.t2j_overlap != 0;
     if (ovl && !x->side) {
-        HIPCHK(hipStreamCreateWithFlags(&x->side, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&x->side_go, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&x->side_done, hipEventDisableTiming));
+        HIPCHK(x->side.create(hipStreamNonBlocking));
+        HIPCHK(x->side_go.create(hipEventDisableTiming));
+        HIPCHK(x->side_done.create(hipEventDisableTiming));
     }
-    hipStream_t ws = ovl ? x->side : s; /* the wave kernel's stream */
-    if (wave) {
-        /* one token workspace per context, like the deep workspace: a wave
-         * pass on another stream waits for the previous one */
-        if (c->ws_t2w_last && c->ws_t2w_last != ws) HIPCHK(hipStreamWaitEvent(ws, c->ws_t2w_done, 0));
-    }
+    hipStream_t ws = ovl ? (hipStream_t)x->side : s; /* the wave kernel's stream */
+    /* one token workspace per context, like the deep workspace: a wave
+     * pass on another stream waits for the previous one */
+    if (wave) HIPCHK(c->t2j_tok.acquire(ws));
     /* this launch's counter set; its deep pass zeroes the other one */
-    uint32_t *const cnt = x->d_counts + (x->t2j_set ? 16u : DG_T2J_DEEP_COUNT);
-    uint32_t *const cnt_next = x->d_counts + (x->t2j_set ? DG_T2J_DEEP_COUNT : 16u);
+    uint32_t *const cnt = x->t2j_cnt.mine();
     T2JParams P;
     memset(&P, 0, sizeof P);
     P.root = root;
     P.opts = opts;
-    P.src = src;
-    P.in_off = in_off;
+    P.src = b.src;
+    P.in_off = b.in_off;
     P.n = n;
-    P.out = out;
-    P.out_off = out_off;
-    P.out_len = out_len;
-    P.ret = ret;
+    P.out = b.out;
+    P.out_off = b.out_off;
+    P.out_len = b.out_len;
+    P.ret = b.ret;
     P.blob = d->d_blob;
     P.hdr = d->hdr;
     P.side = d->d_side;
     P.deep_list = x->t2j_list;
-    P.deep_count = cnt;
-    P.reset_counts = cnt_next;
-    P.ws = c->ws_t2j;
+    P.deep_count = cnt + T2J_DEEPQ;
+    P.reset_counts = x->t2j_cnt.other();
+    P.ws = c->t2j_deep.ws;
     P.stats = c->d_stats;
-    P.aux = (opts & DG_T2J_SKIP_RESP_BASE) ? aux : nullptr;
-    P.ans_tab = (opts & DG_T2J_HM) ? ans : nullptr;
-    P.ans_bytes = ans_bytes;
+    P.aux = (opts & DG_T2J_SKIP_RESP_BASE) ? b.aux : nullptr;
+    P.ans_tab = (opts & DG_T2J_HM) ? b.hm.vm : nullptr;
+    P.ans_bytes = b.hm.bytes;
     hipError_t e = hipSuccess;
     if (wave) {
         T2JParams P1 = P;
         P1.big_list = x->t2j_big;
-        P1.big_count = cnt + 1;
+        P1.big_count = cnt + T2J_BIG;
         P1.big_min = wmin;
         if (ovl) {
             launch_t2j_route(n, s, P1); /* the long ones, by length */
@@ -116,12 +107,12 @@ static int t2j_launch(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t 
         if (e == hipSuccess) launch_t2j_pass(n, s, P1, 1); /* the short ones: full waves */
         T2WParams W;
         W.list = x->t2j_big;
-        W.count = cnt + 1;
-        W.queue = cnt + 2;
+        W.count = cnt + T2J_BIG;
+        W.queue = cnt + T2J_WAVEQ;
         W.bail_list = x->t2j_bail;
-        W.bail_count = cnt + 3;
+        W.bail_count = cnt + T2J_BAIL;
         const uint32_t wblocks = (uint32_t)c->n_cu * T2W_BPC; /* the token regions are sized for it */
-        W.tok = c->ws_t2w;
+        W.tok = c->t2j_tok.ws;
         W.side_len = (uint32_t)d->side_len;
         if (e == hipSuccess && (e = hipGetLastError()) == hipSuccess) {
             launch_t2j_wave(wblocks, ws, P, W);
@@ -134,38 +125,26 @@ static int t2j_launch(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t 
             launch_t2j_list(64, ws, P3);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) {
-            if (!c->ws_t2w_done) e = hipEventCreateWithFlags(&c->ws_t2w_done, hipEventDisableTiming | hipEventDisableSystemFence);
-            if (e == hipSuccess) e = hipEventRecord(c->ws_t2w_done, ws);
-            if (e == hipSuccess) c->ws_t2w_last = ws;
-        }
+        if (e == hipSuccess) e = c->t2j_tok.publish(ws);
         if (ovl && e == hipSuccess) { /* the deep pass takes both passes' queue */
             e = hipEventRecord(x->side_done, ws);
             if (e == hipSuccess) e = hipStreamWaitEvent(s, x->side_done, 0);
         }
     } else {
-        launch_t2j_pass(n, s, P, t2j_spread(c, max_len));
+        launch_t2j_pass(n, s, P, t2j_spread(c, b.max_len));
         e = hipGetLastError();
     }
     /* the deep workspace is one per context: a deep pass on another stream
      * than the previous one waits for it (deep messages are rare; the LDS
      * passes of different streams still overlap) */
-    if (e == hipSuccess && c->ws_t2j_last && c->ws_t2j_last != s) e = hipStreamWaitEvent(s, c->ws_t2j_done, 0);
+    if (e == hipSuccess) e = c->t2j_deep.acquire(s);
     if (e == hipSuccess) {
         launch_t2j_deep(s, P);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(c->ws_t2j_done, s);
-    if (e == hipSuccess) c->ws_t2j_last = s;
-    if (e == hipSuccess) {
-        x->t2j_set ^= 1u;
-    } else { /* the deep pass may not have run: both sets cleared */
-        (void)hipMemsetAsync(cnt, 0, 16, s);
-        (void)hipMemsetAsync(cnt_next, 0, 16, s);
-    }
-    HIPCHK(hipEventRecord(x->done, s));
-    x->used = true;
-    x->last = s;
+    if (e == hipSuccess) e = c->t2j_deep.publish(s);
+    x->t2j_cnt.finish(e == hipSuccess, s);
+    HIPCHK(x->publish(s));
     if (e != hipSuccess) return set_err(DG_E_HIP, "t2j launch: %s", hipGetErrorString(e));
     return DG_OK;
 }
@@ -187,18 +166,15 @@ int dg_desc_attach_t2j(dg_desc *d, const void *side, size_t len)
         if ((uint64_t)f[k].key_off + f[k].key_len > h.pool_len || (uint64_t)f[k].name_off + f[k].name_len > h.pool_len ||
             (f[k].key_off & 7) || (f[k].name_off & 7))
             return set_err(DG_E_DESC, "t2j side table: field %u key out of range", k);
-    std::lock_guard<std::mutex> g(d->ctx->mu);
-    HIPCHK(hipSetDevice(d->ctx->device));
-    uint8_t *p;
-    HIPCHK(hipMalloc(&p, len + 16)); /* the kernel reads whole words past a key's end */
+    Entry g(d->ctx, true);
+    if (g.rc) return g.rc;
+    DevArr<uint8_t> p;
+    if (int rc = p.alloc(len + 16)) return rc; /* the kernel reads whole words past a key's end */
     HIPCHK(hipMemcpy(p, side, len, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(p + len, 0, 16));
     HIPCHK(hipDeviceSynchronize()); /* before launches on non-blocking streams read it */
-    if (d->d_side) {
-        HIPCHK(hipDeviceSynchronize()); /* launches in flight may read the old table */
-        (void)hipFree(d->d_side);
-    }
-    d->d_side = p;
+    if (d->d_side) HIPCHK(hipDeviceSynchronize()); /* launches in flight may read the old table */
+    d->d_side = std::move(p); /* the old table, if any, is freed when p goes */
     d->side_len = len;
     return DG_OK;
 }
@@ -207,42 +183,41 @@ int dg_desc_attach_t2j(dg_desc *d, const void *side, size_t len)
  * message (every line its 208 B of JSON touched) at 8-byte alignment */
 uint64_t dg_t2j_slot_bound(uint64_t len) { return (3 * len + 64 + 127) & ~127ull; }
 
-int dg_t2j_batch_device_ml(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_thrift,
-                           const uint64_t *d_in_off, uint64_t n, uint64_t opts, uint8_t *d_out,
-                           const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, void *stream,
-                           uint64_t max_len)
-{
-    if (!c || !d) return set_err(DG_E_INVALID, "null ctx/desc");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return t2j_launch(c, d, root, d_thrift, d_in_off, n, opts, d_out, d_out_off, d_out_len, d_ret, s, max_len);
-}
-
-int dg_t2j_batch_device_aux(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_thrift,
-                            const uint64_t *d_in_off, uint64_t n, uint64_t opts, uint8_t *d_out,
-                            const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, uint64_t *d_aux,
-                            void *stream, uint64_t max_len)
-{
-    if (!c || !d || ((opts & DG_T2J_SKIP_RESP_BASE) && !d_aux)) return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return t2j_launch(c, d, root, d_thrift, d_in_off, n, opts, d_out, d_out_off, d_out_len, d_ret, s, max_len, d_aux);
-}
-
 int dg_t2j_batch_device_cb(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_thrift,
                            const uint64_t *d_in_off, uint64_t n, uint64_t opts, uint8_t *d_out,
                            const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, uint64_t *d_aux,
                            const dg_cb_entry *d_ans, const uint8_t *d_ans_bytes, void *stream, uint64_t max_len)
 {
-    if (!c || !d || ((opts & DG_T2J_SKIP_RESP_BASE) && !d_aux) || (d_ans && !d_ans_bytes))
-        return set_err(DG_E_INVALID, "bad args");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return t2j_launch(c, d, root, d_thrift, d_in_off, n, opts, d_out, d_out_off, d_out_len, d_ret, s, max_len, d_aux,
-                      d_ans, d_ans_bytes);
+    Entry g(c, c && d && !((opts & DG_T2J_SKIP_RESP_BASE) && !d_aux) && !(d_ans && !d_ans_bytes), stream);
+    if (g.rc) return g.rc;
+    BatchArgs b;
+    b.src = d_thrift, b.in_off = d_in_off, b.n = n, b.flags = opts, b.max_len = max_len;
+    b.out = d_out, b.out_off = d_out_off, b.out_len = d_out_len, b.ret = d_ret;
+    b.aux = d_aux, b.hm.vm = d_ans, b.hm.bytes = d_ans_bytes;
+    return t2j_launch(c, d, root, b, g.s);
+}
+
+/* the forms without callback answers, without spans, without max_len */
+int dg_t2j_batch_device_aux(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_thrift,
+                            const uint64_t *d_in_off, uint64_t n, uint64_t opts, uint8_t *d_out,
+                            const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, uint64_t *d_aux,
+                            void *stream, uint64_t max_len)
+{
+    return dg_t2j_batch_device_cb(c, d, root, d_thrift, d_in_off, n, opts, d_out, d_out_off, d_out_len, d_ret, d_aux,
+                                  nullptr, nullptr, stream, max_len);
+}
+
+int dg_t2j_batch_device_ml(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_thrift,
+                           const uint64_t *d_in_off, uint64_t n, uint64_t opts, uint8_t *d_out,
+                           const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, void *stream,
+                           uint64_t max_len)
+{
+    Entry g(c, c && d, stream, "null ctx/desc");
+    if (g.rc) return g.rc;
+    BatchArgs b;
+    b.src = d_thrift, b.in_off = d_in_off, b.n = n, b.flags = opts, b.max_len = max_len;
+    b.out = d_out, b.out_off = d_out_off, b.out_len = d_out_len, b.ret = d_ret;
+    return t2j_launch(c, d, root, b, g.s);
 }
 
 int dg_t2j_batch_device(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *d_thrift, const uint64_t *d_in_off,
@@ -253,10 +228,14 @@ int dg_t2j_batch_device(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_
                                   0);
 }
 
-static int t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *thrift, const uint64_t *in_off,
-                          uint64_t n, uint64_t opts, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
-                          uint64_t *out_need, uint64_t *aux, const dg_cb_tables *cb)
+/* in: host pointers (src, in_off, n, flags = the options, ret, aux) */
+static int t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const BatchArgs &in, const HostOut &o,
+                          const dg_cb_tables *cb)
 {
+    const uint8_t *const thrift = in.src;
+    const uint64_t *const in_off = in.in_off, n = in.n, opts = in.flags;
+    uint8_t *const out = o.out;
+    uint64_t *const out_off = o.out_off, *const ret = in.ret, *const aux = in.aux;
     if (!c || !d || (!thrift && n) || !in_off || !out_off || (!ret && n) ||
         ((opts & DG_T2J_SKIP_RESP_BASE) && n && !aux) || (cb && cb->ans_tab && cb->len && !cb->bytes))
         return set_err(DG_E_INVALID, "bad args");
@@ -264,13 +243,12 @@ static int t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint
     for (uint64_t i = 0; ans && i < n; i++) /* one byte per answer, inside the bytes (read unchecked) */
         if (ans[i].off + ans[i].count > cb->len)
             return set_err(DG_E_INVALID, "callback answers of message %llu outside the bytes", (unsigned long long)i);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    Entry g(c, true);
+    if (g.rc) return g.rc;
     const uint64_t base = in_off[0];
-    std::vector<uint64_t> ioff(n + 1), soff(n + 1);
     std::vector<uint32_t> olen(n);
     std::vector<uint8_t> stage;
-    hipStream_t s = c->stream;
+    const hipStream_t s = g.s;
     int rc;
     /* pass 0: every message in a dg_t2j_slot_bound slot; pass 1: the
      * overflowed ones again, each in a slot of exactly the size it reported */
@@ -288,15 +266,15 @@ static int t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint
             io[k + 1] = io[k] + len;
             so[k + 1] = so[k] + (pass == 0 ? dg_t2j_slot_bound(len) : ((uint64_t)olen[i] + 64 + 7) & ~7ull);
         }
-        if ((rc = grow(c->d_json, c->d_json_cap, io[m] + 64))) return rc;
-        if ((rc = grow(c->d_in_off, c->d_in_cap, m + 1))) return rc;
-        if ((rc = grow(c->d_out, c->d_out_cap, so[m] + 64))) return rc;
-        if ((rc = grow(c->d_out_off, c->d_oo_cap, m + 1))) return rc;
-        if ((rc = grow(c->d_out_len, c->d_ol_cap, m + 1))) return rc;
-        if ((rc = grow(c->d_ret, c->d_ret_cap, m + 1))) return rc;
-        if (aux && (rc = grow(c->d_aux, c->d_aux_cap, m + 1))) return rc;
+        if ((rc = c->d_json.grow(io[m] + 64))) return rc;
+        if ((rc = c->d_in_off.grow(m + 1))) return rc;
+        if ((rc = c->d_out.grow(so[m] + 64))) return rc;
+        if ((rc = c->d_out_off.grow(m + 1))) return rc;
+        if ((rc = c->d_out_len.grow(m + 1))) return rc;
+        if ((rc = c->d_ret.grow(m + 1))) return rc;
+        if (aux && (rc = c->d_aux.grow(m + 1))) return rc;
         if (ans) { /* [m entries | the answer bytes] */
-            if ((rc = grow(c->d_cb, c->d_cb_cap, 8 * m + cb->len + 8))) return rc;
+            if ((rc = c->d_cb.grow(8 * m + cb->len + 8))) return rc;
             std::vector<dg_cb_entry> e(m);
             for (uint64_t k = 0; k < m; k++) e[k] = ans[todo[k]];
             HIPCHK(hipMemcpyAsync(c->d_cb, e.data(), 8 * m, hipMemcpyHostToDevice, s));
@@ -313,10 +291,12 @@ static int t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint
         HIPCHK(hipMemsetAsync(c->d_json + io[m], 0, 64, s));
         HIPCHK(hipMemcpyAsync(c->d_in_off, io.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(c->d_out_off, so.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
-        if ((rc = t2j_launch(c, d, root, c->d_json, c->d_in_off, m, opts, c->d_out, c->d_out_off, c->d_out_len,
-                             c->d_ret, s, max_len, aux ? c->d_aux : nullptr,
-                             ans ? (const dg_cb_entry *)(const void *)c->d_cb : nullptr, ans ? c->d_cb + 8 * m : nullptr)))
-            return rc;
+        BatchArgs b;
+        b.src = c->d_json, b.in_off = c->d_in_off, b.n = m, b.flags = opts, b.max_len = max_len;
+        b.out = c->d_out, b.out_off = c->d_out_off, b.out_len = c->d_out_len, b.ret = c->d_ret;
+        if (aux) b.aux = c->d_aux;
+        if (ans) b.hm.vm = (const dg_cb_entry *)(const void *)(uint8_t *)c->d_cb, b.hm.bytes = c->d_cb + 8 * m;
+        if ((rc = t2j_launch(c, d, root, b, s))) return rc;
         std::vector<uint64_t> r(m), ax(aux ? m : 0);
         std::vector<uint32_t> l(m);
         if (aux) HIPCHK(hipMemcpyAsync(ax.data(), c->d_aux, m * 8, hipMemcpyDeviceToHost, s));
@@ -349,32 +329,35 @@ static int t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint
         total += olen[i];
         out_off[i + 1] = total;
     }
-    if (out_need) *out_need = total;
-    if (total > out_cap || (!out && total)) return set_err(DG_E_NOMEM, "output needs %llu bytes", (unsigned long long)total);
+    if (o.out_need) *o.out_need = total;
+    if (total > o.out_cap || (!out && total)) return set_err(DG_E_NOMEM, "output needs %llu bytes", (unsigned long long)total);
     for (uint64_t i = 0; i < n; i++)
         if (olen[i]) memcpy(out + out_off[i], stage.data() + slot_of[i], olen[i]);
     return DG_OK;
-}
-
-int dg_t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *thrift, const uint64_t *in_off,
-                      uint64_t n, uint64_t opts, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
-                      uint64_t *out_need)
-{
-    return t2j_batch_host(c, d, root, thrift, in_off, n, opts, out, out_cap, out_off, ret, out_need, nullptr, nullptr);
-}
-
-int dg_t2j_batch_host_aux(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *thrift, const uint64_t *in_off,
-                          uint64_t n, uint64_t opts, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
-                          uint64_t *out_need, uint64_t *aux)
-{
-    return t2j_batch_host(c, d, root, thrift, in_off, n, opts, out, out_cap, out_off, ret, out_need, aux, nullptr);
 }
 
 int dg_t2j_batch_host_cb(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *thrift, const uint64_t *in_off,
                          uint64_t n, uint64_t opts, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
                          uint64_t *out_need, uint64_t *aux, const dg_cb_tables *cb)
 {
-    return t2j_batch_host(c, d, root, thrift, in_off, n, opts, out, out_cap, out_off, ret, out_need, aux, cb);
+    BatchArgs in;
+    in.src = thrift, in.in_off = in_off, in.n = n, in.flags = opts, in.ret = ret, in.aux = aux;
+    return t2j_batch_host(c, d, root, in, HostOut{out, out_cap, out_off, out_need}, cb);
+}
+
+int dg_t2j_batch_host_aux(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *thrift, const uint64_t *in_off,
+                          uint64_t n, uint64_t opts, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
+                          uint64_t *out_need, uint64_t *aux)
+{
+    return dg_t2j_batch_host_cb(c, d, root, thrift, in_off, n, opts, out, out_cap, out_off, ret, out_need, aux, nullptr);
+}
+
+int dg_t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const uint8_t *thrift, const uint64_t *in_off,
+                      uint64_t n, uint64_t opts, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
+                      uint64_t *out_need)
+{
+    return dg_t2j_batch_host_cb(c, d, root, thrift, in_off, n, opts, out, out_cap, out_off, ret, out_need, nullptr,
+                                nullptr);
 }
 
 }  // extern "C"

@@ -12,8 +12,19 @@ using namespace dg;
 
 struct dg_path {
     dg_ctx *ctx;
-    uint8_t *d_blob;
+    DevArr<uint8_t> d_blob;
     dg_path_hdr hdr;
+};
+
+/* one batch of messages (device pointers) and where its records go */
+struct TGetBatch {
+    const uint8_t *src;
+    const uint64_t *in_off;
+    uint64_t n;
+    dg_tget_rec *rec;
+    uint64_t *val_off; /* optional, with val_len */
+    uint32_t *val_len;
+    uint64_t max_len;
 };
 
 static const uint64_t TGET_WS = (uint64_t)TG_DEEP_DEPTH * TG_DEEP_LANES * 8;
@@ -38,56 +49,54 @@ static uint32_t tget_spread(const dg_ctx *c, uint64_t max_len)
  * and the deep frames are one per context: a launch on another stream than
  * the previous one waits for it. Launches alternate between the counters and
  * each deep pass zeroes the other one (no memset per launch). */
-static int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const uint8_t *src, const uint64_t *in_off,
-                       uint64_t n, dg_tget_rec *rec, uint64_t *val_off, uint32_t *val_len, hipStream_t s,
-                       uint64_t max_len)
+static int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const TGetBatch &b, hipStream_t s)
 {
+    const uint64_t n = b.n;
     if (n == 0) return DG_OK;
-    if (!src || !in_off || !rec) return set_err(DG_E_INVALID, "null buffer");
-    if ((uintptr_t)rec & 15) return set_err(DG_E_INVALID, "records not 16-byte aligned"); /* one store each */
+    if (!b.src || !b.in_off || !b.rec) return set_err(DG_E_INVALID, "null buffer");
+    if ((uintptr_t)b.rec & 15) return set_err(DG_E_INVALID, "records not 16-byte aligned"); /* one store each */
     const uint64_t pairs = n * ps->hdr.n_paths;
     if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
         return set_err(DG_E_INVALID, "batch of %llu messages x %u paths", (unsigned long long)n, ps->hdr.n_paths);
-    if (!c->ws_tget) {
-        HIPCHK(hipMalloc(&c->ws_tget, TGET_WS));
-        HIPCHK(hipMalloc(&c->tget_cnt, 16));
-        HIPCHK(hipMemset(c->tget_cnt, 0, 16));
+    int rc;
+    if (!c->tget.ws) {
+        if ((rc = c->tget.ws.alloc(TGET_WS)) || (rc = c->tget_cnt_buf.alloc(4))) return rc;
+        HIPCHK(hipMemset(c->tget_cnt_buf, 0, 16));
         HIPCHK(hipDeviceSynchronize()); /* before a non-blocking stream counts on it */
-        HIPCHK(hipEventCreateWithFlags(&c->tget_done, hipEventDisableTiming | hipEventDisableSystemFence));
+        c->tget_cnt.set[0] = c->tget_cnt_buf;
+        c->tget_cnt.set[1] = c->tget_cnt_buf + 1;
+        c->tget_cnt.bytes = 4;
     }
-    if (c->tget_list_cap < pairs) { /* the previous launch may still fill the old list */
-        if (c->tget_last) HIPCHK(hipEventSynchronize(c->tget_done));
-        int rc = grow(c->tget_list, c->tget_list_cap, pairs);
-        if (rc) return rc;
+    if (c->tget_list.cap < pairs) { /* the previous launch may still fill the old list */
+        HIPCHK(c->tget.wait_host());
+        if ((rc = c->tget_list.grow(pairs))) return rc;
     }
-    if (c->tget_last && c->tget_last != s) HIPCHK(hipStreamWaitEvent(s, c->tget_done, 0));
+    HIPCHK(c->tget.acquire(s));
     TGParams A;
     memset(&A, 0, sizeof A);
-    A.src = src;
-    A.in_off = in_off;
+    A.src = b.src;
+    A.in_off = b.in_off;
     A.pairs = pairs;
     A.P = ps->hdr.n_paths;
     A.root_type = root_type;
     A.blob = ps->d_blob;
     A.off_steps = ps->hdr.off_steps;
     A.off_pool = ps->hdr.off_pool;
-    A.rec = rec;
-    A.val_off = val_off;
-    A.val_len = val_len;
+    A.rec = b.rec;
+    A.val_off = b.val_off;
+    A.val_len = b.val_len;
     A.deep_list = c->tget_list;
-    A.deep_count = c->tget_cnt + c->tget_set;
-    A.reset_count = c->tget_cnt + (c->tget_set ^ 1u);
-    A.ws = (uint64_t *)(void *)c->ws_tget;
-    launch_tget_pass(s, A, tget_spread(c, max_len));
+    A.deep_count = c->tget_cnt.mine();
+    A.reset_count = c->tget_cnt.other();
+    A.ws = (uint64_t *)(void *)c->tget.ws;
+    launch_tget_pass(s, A, tget_spread(c, b.max_len));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         launch_tget_deep(s, A);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) c->tget_set ^= 1u;
-    else (void)hipMemsetAsync(c->tget_cnt, 0, 16, s); /* the deep pass may not have run: both cleared */
-    HIPCHK(hipEventRecord(c->tget_done, s));
-    c->tget_last = s;
+    c->tget_cnt.finish(e == hipSuccess, s);
+    HIPCHK(c->tget.publish(s));
     if (e != hipSuccess) return set_err(DG_E_HIP, "tget launch: %s", hipGetErrorString(e));
     return DG_OK;
 }
@@ -131,33 +140,26 @@ int dg_path_create(dg_ctx *c, const void *blob, size_t len, dg_path **out)
             if (!key && st.key_len) return set_err(DG_E_ARG, "path %u step %u: key_len on a keyless step", k, s);
         }
     }
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    uint8_t *p;
-    HIPCHK(hipMalloc(&p, (size_t)h.total_len + 16)); /* keys are compared 16 bytes at a time */
-    hipError_t e = hipMemcpy(p, blob, h.total_len, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(p + h.total_len, 0, 16);
-    if (e == hipSuccess) e = hipDeviceSynchronize(); /* before launches on non-blocking streams read it */
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return set_err(DG_E_HIP, "path upload: %s", hipGetErrorString(e));
-    }
-    dg_path *ps = new dg_path();
+    Entry g(c, true);
+    if (g.rc) return g.rc;
+    std::unique_ptr<dg_path> ps(new dg_path());
     ps->ctx = c;
-    ps->d_blob = p;
     ps->hdr = h;
-    *out = ps;
+    if (int rc = ps->d_blob.alloc((size_t)h.total_len + 16)) return rc; /* keys are compared 16 bytes at a time */
+    hipError_t e = hipMemcpy(ps->d_blob, blob, h.total_len, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(ps->d_blob + h.total_len, 0, 16);
+    if (e == hipSuccess) e = hipDeviceSynchronize(); /* before launches on non-blocking streams read it */
+    if (e != hipSuccess) return set_err(DG_E_HIP, "path upload: %s", hipGetErrorString(e));
+    *out = ps.release();
     return DG_OK;
 }
 
 void dg_path_destroy(dg_path *p)
 {
     if (!p) return;
-    {
-        std::lock_guard<std::mutex> g(p->ctx->mu);
-        (void)hipSetDevice(p->ctx->device);
-        (void)hipFree(p->d_blob);
-    }
+    Entry g(p->ctx, true);
+    p->d_blob.reset(); /* under the context lock, on its device */
+    g.lk.unlock();
     delete p;
 }
 
@@ -167,11 +169,9 @@ int dg_tget_batch_device(dg_ctx *c, const dg_path *ps, uint8_t root_type, const 
                          const uint64_t *d_in_off, uint64_t n, dg_tget_rec *d_rec, uint64_t *d_val_off,
                          uint32_t *d_val_len, void *stream, uint64_t max_len)
 {
-    if (!c || !ps || ps->ctx != c) return set_err(DG_E_INVALID, "null ctx/paths, or paths of another context");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return tget_launch(c, ps, root_type, d_thrift, d_in_off, n, d_rec, d_val_off, d_val_len, s, max_len);
+    Entry g(c, c && ps && ps->ctx == c, stream, "null ctx/paths, or paths of another context");
+    if (g.rc) return g.rc;
+    return tget_launch(c, ps, root_type, TGetBatch{d_thrift, d_in_off, n, d_rec, d_val_off, d_val_len, max_len}, g.s);
 }
 
 int dg_tget_batch_host(dg_ctx *c, const dg_path *ps, uint8_t root_type, const uint8_t *thrift, const uint64_t *in_off,
@@ -180,8 +180,8 @@ int dg_tget_batch_host(dg_ctx *c, const dg_path *ps, uint8_t root_type, const ui
     if (!c || !ps || ps->ctx != c) return set_err(DG_E_INVALID, "null ctx/paths, or paths of another context");
     if (n == 0) return DG_OK;
     if (!thrift || !in_off || !rec) return set_err(DG_E_INVALID, "null buffer");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    Entry g(c, true);
+    if (g.rc) return g.rc;
     const uint64_t base = in_off[0], total = in_off[n] - base, pairs = n * ps->hdr.n_paths;
     std::vector<uint64_t> io(n + 1);
     uint64_t max_len = 0;
@@ -191,17 +191,16 @@ int dg_tget_batch_host(dg_ctx *c, const dg_path *ps, uint8_t root_type, const ui
         if (i) max_len = std::max<uint64_t>(max_len, io[i] - io[i - 1]);
     }
     int rc;
-    hipStream_t s = c->stream;
-    if ((rc = grow(c->d_json, c->d_json_cap, total + 64))) return rc;
-    if ((rc = grow(c->d_in_off, c->d_in_cap, n + 1))) return rc;
-    if ((rc = grow(c->d_out, c->d_out_cap, pairs * sizeof(dg_tget_rec) + 64))) return rc;
+    const hipStream_t s = g.s;
+    if ((rc = c->d_json.grow(total + 64))) return rc;
+    if ((rc = c->d_in_off.grow(n + 1))) return rc;
+    if ((rc = c->d_out.grow(pairs * sizeof(dg_tget_rec) + 64))) return rc;
     if (total) HIPCHK(hipMemcpyAsync(c->d_json, thrift + base, total, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(c->d_json + total, 0, 64, s));
     HIPCHK(hipMemcpyAsync(c->d_in_off, io.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s)); /* io is a local */
-    if ((rc = tget_launch(c, ps, root_type, c->d_json, c->d_in_off, n, (dg_tget_rec *)(void *)c->d_out, nullptr,
-                          nullptr, s, max_len)))
-        return rc;
+    const TGetBatch b{c->d_json, c->d_in_off, n, (dg_tget_rec *)(void *)c->d_out, nullptr, nullptr, max_len};
+    if ((rc = tget_launch(c, ps, root_type, b, s))) return rc;
     HIPCHK(hipMemcpyAsync(rec, c->d_out, pairs * sizeof(dg_tget_rec), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return DG_OK;

@@ -112,8 +112,10 @@ def test_two_streams_one_context_vs_oracle(cfg):
 
 
 def test_many_streams_share_scratch_in_order():
-    """More streams than the per-context scratch cap (8): shared scratches
-    order the launches with events; results stay exact."""
+    """Twelve streams of one context launched without a synchronisation in
+    between; results stay exact. Twelve is below the per-context scratch cap
+    (DG_MAX_SCRATCH = 40), so every stream has a scratch of its own here;
+    test_streams_past_the_scratch_cap shares them."""
     import torch
     fl = T.flatten(W.nesting_i64_desc())
     msgs = W.gen_nested_batch(random.Random(8), 12 * 200)
@@ -135,6 +137,103 @@ def test_many_streams_share_scratch_in_order():
         assert got_r == er and got_o == eo
     finally:
         ctx.close()
+
+
+def test_streams_past_the_scratch_cap():
+    """DG_MAX_SCRATCH + 2 streams of one context, a batch each, launched with
+    no synchronisation in between, two rounds: streams 41 and 42 take scratches
+    of other streams round robin, and in the second round every one of those
+    is taken by a stream that did not use it last, so each launch has to wait
+    for the scratch's previous one. Every message stays exact."""
+    import torch
+    nstreams = 40 + 2  # DG_MAX_SCRATCH (host_internal.h) + 2
+    fl = T.flatten(W.nesting_i64_desc())
+    msgs = W.gen_nested_batch(random.Random(9), nstreams * 8)
+    er, eo = _oracle_all(fl, msgs)
+    ctx = conv.Context(0)
+    try:
+        dh = ctx.desc(fl)
+        bs = [DevBatch(msgs[i:i + 8]) for i in range(0, len(msgs), 8)]
+        streams = [torch.cuda.Stream() for _ in bs]
+        for rnd in range(2):
+            for b in bs:
+                b.out_len.zero_()
+                b.ret.fill_(-1)
+            torch.cuda.synchronize()
+            for b, s in zip(bs, streams):
+                b.launch(ctx, dh, fl.root_type, 1, s.cuda_stream)
+            torch.cuda.synchronize()
+            got_r, got_o = [], []
+            for b in bs:
+                r, o = b.results()
+                got_r += r
+                got_o += o
+            assert got_r == er and got_o == eo, rnd
+    finally:
+        ctx.close()
+
+
+def _free_bytes():
+    import torch
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    return torch.cuda.mem_get_info()[0]
+
+
+def test_context_lifecycle_returns_its_memory():
+    """Twelve contexts in a row, each used through every family of entry
+    points (host batch, device batch on a second stream, t2j with its ~100 MB
+    deep frames, a path lookup, the packing scan, the chunked host pipeline)
+    and closed. The device's free memory may not fall between the second and
+    the twelfth close by as much as ONE context's first use takes: a context
+    that kept even its t2j workspace would exceed that ten times over, and
+    allocator granularity does not reach it."""
+    import torch
+    from dynamicgo_amd import generic as G, t2j
+    td = W.nesting_i64_desc()
+    fl = T.flatten(td)
+    msgs = W.gen_nested_batch(random.Random(10), 3)
+    er, eo = _oracle_all(fl, msgs)
+    side = torch.cuda.Stream()
+    b = DevBatch(msgs)
+    d_dst = torch.zeros(int(b.slots[-1]) + 64, dtype=torch.uint8, device="cuda:0")
+    d_doff = torch.zeros(len(msgs) + 1, dtype=torch.int64, device="cuda:0")
+    d_rec = torch.zeros((len(msgs), 1, 4), dtype=torch.int32, device="cuda:0")
+    before = _free_bytes()
+    marks = {}
+    for it in range(1, 13):
+        ctx = conv.Context(0)
+        try:
+            cv = conv.BinaryConv(conv.Options(), ctx=ctx)
+            outs, rets = cv.do_batch(td, msgs)                      # dg_j2t_batch_host
+            assert [int(r) for r in rets] == er and outs == eo
+            b.launch(ctx, ctx.desc(fl), fl.root_type, 1, side.cuda_stream)  # dg_j2t_batch_device
+            side.synchronize()
+            assert b.results() == (er, eo)
+            js, jr = t2j.BinaryConv(conv.Options(), ctx=ctx).do_batch(td, eo)  # dg_t2j_batch_host
+            assert not any(int(r) for r in jr) and all(js)
+            thr = torch.from_numpy(np.frombuffer(b"".join(eo) + bytes(16), dtype=np.uint8).copy()).cuda()
+            t_off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(o) for o in eo])]).astype(np.int64)).cuda()
+            with G.PathSet([[G.PathFieldId(1)]], ctx=ctx) as ps:     # dg_tget_batch_device
+                G.get_by_path_device(ps, thr, t_off, len(eo), d_rec)
+                torch.cuda.synchronize()
+            _lib.check(_lib.lib().dg_pack_device_scan(ctx.h, b.out.data_ptr(), b.out_off.data_ptr(),
+                                                      b.out_len.data_ptr(), b.n, d_dst.data_ptr(), d_doff.data_ptr(),
+                                                      side.cuda_stream))
+            side.synchronize()
+            assert int(d_doff[-1].item()) == sum(len(o) for o in eo)
+            outs, rets = cv.do_batch(td, msgs, chunks=2)            # dg_j2t_pipeline_host
+            assert [int(r) for r in rets] == er and outs == eo
+            del thr, t_off
+            if it == 1:
+                marks["first use"] = before - _free_bytes()
+        finally:
+            ctx.close()
+        if it in (2, 12):
+            marks[it] = _free_bytes()
+    print("first use %d bytes, free after 2: %d, after 12: %d" % (marks["first use"], marks[2], marks[12]))
+    assert marks["first use"] > 100 << 20  # the t2j deep frames alone
+    assert marks[2] - marks[12] < marks["first use"]
 
 
 def test_desc_create_device_vs_oracle():

@@ -347,6 +347,76 @@ def test_device_entry_point_ml(chk):
         assert (int(ret[i]), out[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes()) == (er, eo)
 
 
+def test_two_streams_share_the_context_workspaces(chk):
+    """Four chunks launched alternately on two streams of ONE context through
+    dg_t2j_batch_device_ml, three rounds, no synchronisation between the
+    launches. Every chunk holds a message nested deeper than the 12 LDS frames
+    (only the deep pass, over the context's one set of deep frames, converts
+    it), messages longer than t2j_wave_min (the wave kernel, over the context's
+    one set of token regions) and short ones; the streams have a scratch each,
+    so what orders them is the workspaces' own events. Byte-exact against the
+    reference. (dg_ctx_stats does not count the t2j deep pass; that it ran
+    shows in the deep messages' JSON, which no other pass can produce.)"""
+    import torch
+    sd = T.StructDescriptor("Node")
+    td = T.TypeDescriptor(t2jgen.STRUCT, "Node", struct=sd)
+    sd.add_field(T.FieldDescriptor(1, "v", T.builtin("i32"), T.OPTIONAL))
+    sd.add_field(T.FieldDescriptor(2, "next", td, T.OPTIONAL))
+    sd.add_field(T.FieldDescriptor(3, "s", T.builtin("string"), T.OPTIONAL))
+    fl = T.flatten(td)
+    side = T.flatten_t2j(fl)
+    rng = random.Random(47)
+
+    def long_msg():  # a string field of 300 to 700 bytes, then v
+        txt = bytes(rng.choice(b'abc"\\\n xyz') for _ in range(rng.randrange(300, 700)))
+        return b"\x0b\x00\x03" + struct.pack(">i", len(txt)) + txt + b"\x08\x00\x01\x00\x00\x00\x09\x00"
+
+    chunks = []
+    for k in range(4):
+        msgs = [t2jgen.chain_thrift(rng.randrange(1, 6)) for _ in range(64)]
+        msgs[5 + k] = t2jgen.chain_thrift(20)
+        msgs[40 - k] = t2jgen.chain_thrift(13 + k)
+        for j in (0, 17, 33 + k, 63):
+            msgs[j] = long_msg()
+        chunks.append(msgs)
+    assert all(max(map(len, c)) > 256 for c in chunks)
+    want = [[chk.t2j(fl, side, m, 0) for m in c] for c in chunks]
+    assert all(er == 0 and eo for c in want for er, eo in c)
+    dev = torch.device("cuda:0")
+    ctx = conv.Context(0)
+    try:
+        dh = ctx.desc_t2j(fl)
+        assert ctx.get_knob("t2j_wave_min") == 256
+        bufs = []
+        for msgs in chunks:
+            a, off = W.arena(msgs)
+            lens = np.diff(off).astype(np.int64)
+            oo = np.zeros(len(msgs) + 1, dtype=np.int64)
+            np.cumsum((lens * 3 + 64 + 7) // 8 * 8, out=oo[1:])
+            bufs.append((torch.from_numpy(a).to(dev), torch.from_numpy(off.astype(np.int64)).to(dev),
+                         torch.from_numpy(oo).to(dev), torch.zeros(int(oo[-1]) + 64, dtype=torch.uint8, device=dev),
+                         torch.zeros(len(msgs), dtype=torch.int32, device=dev),
+                         torch.zeros(len(msgs), dtype=torch.int64, device=dev), oo, int(lens.max())))
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        for rnd in range(3):
+            for d_src, d_in, d_oo, d_out, d_ol, d_ret, oo, ml in bufs:
+                d_out.zero_()
+                d_ol.zero_()
+                d_ret.fill_(-1)
+            torch.cuda.synchronize()
+            for k, (d_src, d_in, d_oo, d_out, d_ol, d_ret, oo, ml) in enumerate(bufs):
+                _lib.check(_lib.lib().dg_t2j_batch_device_ml(
+                    ctx.h, dh, fl.root_type, d_src.data_ptr(), d_in.data_ptr(), 64, 0, d_out.data_ptr(),
+                    d_oo.data_ptr(), d_ol.data_ptr(), d_ret.data_ptr(), streams[(k + rnd) % 2].cuda_stream, ml))
+            torch.cuda.synchronize()
+            for k, (d_src, d_in, d_oo, d_out, d_ol, d_ret, oo, ml) in enumerate(bufs):
+                out, ol, ret = d_out.cpu().numpy(), d_ol.cpu().numpy(), d_ret.cpu().numpy()
+                got = [(int(ret[i]), out[int(oo[i]):int(oo[i]) + int(ol[i])].tobytes()) for i in range(64)]
+                assert got == want[k], (rnd, k)
+    finally:
+        ctx.close()
+
+
 def _example3(kind):
     import os
     idl = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "idl", "example3.thrift")
