@@ -40,14 +40,16 @@ def _run_rows(rows, flats, extra=0):
     return bad
 
 
-def _raw_batch(flat, msgs, flags):
-    """dg_j2t_batch_host with an explicit flag word."""
+def _raw_batch(flat, msgs, flags, cap=None):
+    """dg_j2t_batch_host with an explicit flag word (cap: the output buffer's
+    size, for descriptors that write far more than the messages hold)."""
     import ctypes as C
     from dynamicgo_amd import _lib
     ctx = conv.default_context()
     n = len(msgs)
     a, off = W.arena(msgs)
-    cap = int(off[-1]) * 16 + 64 * n + 65536
+    if cap is None:
+        cap = int(off[-1]) * 16 + 64 * n + 65536
     out = np.zeros(cap, dtype=np.uint8)
     oo = np.zeros(n + 1, dtype=np.uint64)
     rets = np.zeros(n, dtype=np.uint64)
