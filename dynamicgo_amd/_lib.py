@@ -22,7 +22,8 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_agg_gateway_drive", "dg_j2t_pipeline_host", "dg_bench_device", "dg_desc_attach_t2j", "dg_t2j_slot_bound", "dg_t2j_batch_device", "dg_t2j_batch_device_ml",
            "dg_t2j_batch_host", "dg_t2j_batch_device_aux", "dg_t2j_batch_host_aux",
            "dg_t2j_batch_device_cb", "dg_t2j_batch_host_cb",
-           "dg_path_create", "dg_path_destroy", "dg_path_count", "dg_tget_batch_device", "dg_tget_batch_host"]
+           "dg_path_create", "dg_path_destroy", "dg_path_count", "dg_tget_batch_device", "dg_tget_batch_host",
+           "dg_cut_create", "dg_cut_destroy", "dg_cut_slot_bound", "dg_cut_batch_device", "dg_cut_batch_host"]
 
 _lib = None
 
@@ -108,6 +109,11 @@ def lib() -> C.CDLL:
         "dg_path_count": (u32, [vp]),
         "dg_tget_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, u64]),
         "dg_tget_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp]),
+        "dg_cut_create": (i32, [vp, C.c_char_p, sz, C.POINTER(vp)]),
+        "dg_cut_destroy": (None, [vp]),
+        "dg_cut_slot_bound": (u64, [vp, u64, u64]),
+        "dg_cut_batch_device": (i32, [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, u64]),
+        "dg_cut_batch_host": (i32, [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, P64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

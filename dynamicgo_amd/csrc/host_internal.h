@@ -4,7 +4,7 @@
  * orders a shared buffer across streams, the context, descriptor and
  * per-stream scratch records, the entry guard, the argument records of one
  * batch and the error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host and j2t_pipe use them).
+ * tget_host, cut_host and j2t_pipe use them).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -260,6 +260,7 @@ struct Knobs {
     int64_t t2j_wave_min = 256; /* t2j messages longer than this take the wave kernel (0: never); r4k t2j-c3: 128 / 192 / 256 / 384 / 512 / 1024 -> 66.1 / 66.5 / 66.3 / 59.4 / 53.7 / 23.3 GB/s */
     int64_t flat_wrap = -1;     /* the flat kernel's wrapped mode for roots that wrap a flat struct (0: off) */
     int64_t tget_spread = 0;    /* tget: lanes per (message, path) pair, 0 = from the longest message (tget_host.hip) */
+    int64_t cut_wave_min = 4096; /* cut: messages at least this long take the wave route (0: all of them); ~1.1 KB x 65 536: 256 / 1024 / 4096 / 16384 -> 29.5 / 44.0 / 227.2 / 227.6 GB/s; ~83 KB x 4 096: lane 23.5, wave 26.5 */
 };
 
 /* one chunk in flight of dg_j2t_pipeline_host (j2t_pipe.hip) */
@@ -297,6 +298,11 @@ struct dg_ctx {
     SharedWs tget;
     DevArr<uint32_t> tget_list, tget_cnt_buf;
     AltCounters tget_cnt;
+    /* cut (cut_host.hip): the wave route's queue and its two alternating
+     * counters, one per context like tget's */
+    StreamOrder cut;
+    DevArr<uint32_t> cut_list, cut_cnt_buf;
+    AltCounters cut_cnt;
     /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB) */
     SharedWs t2j_tok;
     /* t2j deep pass: T2J_DEEP_DEPTH frames per lane (about 100 MB, allocated
@@ -425,3 +431,9 @@ __attribute__((visibility("hidden"))) int scratch_for(dg_ctx *c, hipStream_t s, 
 __attribute__((visibility("hidden"))) int dg_i_convert_pack(dg_ctx *c, const dg_desc *d, uint32_t root,
                                                             const BatchArgs &b, uint8_t *packed, uint64_t *pack_off,
                                                             hipStream_t s, const PackChain &ch);
+
+/* dg_pack_device_scan on stream s with the ctx mutex held: b's out / out_off /
+ * out_len / n, and with b.ret set the messages whose status is not 0 pack as
+ * nothing */
+__attribute__((visibility("hidden"))) int dg_i_pack_scan(dg_ctx *c, hipStream_t s, const BatchArgs &b, uint8_t *d_dst,
+                                                         uint64_t *d_dst_off);

@@ -118,6 +118,7 @@ static int64_t *knob_ref(dg_ctx *c, const char *name)
     if (!strcmp(name, "t2j_overlap")) return &K.t2j_overlap;
     if (!strcmp(name, "flat_wrap")) return &K.flat_wrap;
     if (!strcmp(name, "tget_spread")) return &K.tget_spread;
+    if (!strcmp(name, "cut_wave_min")) return &K.cut_wave_min;
     return nullptr;
 }
 
@@ -152,7 +153,7 @@ int dg_ctx_create(int device, dg_ctx **out)
         {"DG_FLAT", "flat"}, {"DG_WAVE_MIN", "wave_min"}, {"DG_WAVE_OCC", "wave_occ"},
         {"DG_SMALL_MPW", "small_mpw"}, {"DG_LIST_BLOCKS", "list_blocks"}, {"DG_T2J_SPREAD", "t2j_spread"},
         {"DG_T2J_WAVE_MIN", "t2j_wave_min"}, {"DG_T2J_OVERLAP", "t2j_overlap"}, {"DG_FLAT_WRAP", "flat_wrap"},
-        {"DG_TGET_SPREAD", "tget_spread"}};
+        {"DG_TGET_SPREAD", "tget_spread"}, {"DG_CUT_WAVE_MIN", "cut_wave_min"}};
     for (const auto &e : envk) {
         const char *v = getenv(e.env);
         if (v && *v) *knob_ref(c.get(), e.name) = strtoll(v, nullptr, 10);
@@ -990,6 +991,11 @@ static int pack_scan_nolock(dg_ctx *c, hipStream_t s, const BatchArgs &b, const 
 }
 
 }  // extern "C"
+
+int dg_i_pack_scan(dg_ctx *c, hipStream_t s, const BatchArgs &b, uint8_t *d_dst, uint64_t *d_dst_off)
+{
+    return pack_scan_nolock(c, s, b, nullptr, d_dst, d_dst_off);
+}
 
 /* conversion + packing of one batch on stream s (failed and overflowed
  * messages pack as nothing), for the pipelined host paths (j2t_pipe.hip) */

@@ -1,4 +1,7 @@
-"""Batched GetByPath over Thrift-binary messages on the GPU: the reference's
+"""thrift/generic on the GPU. Batched MarshalTo ("cutting", Value.MarshalTo,
+value.go:375-552; the second half of this module: compile_cut, CutPlan,
+marshal_to_batch, marshal_to_device), and
+batched GetByPath over Thrift-binary messages: the reference's
 thrift/generic Node.GetByPath / Value.GetByPath (node.go:431-484,
 value.go:102-161) for every message of a batch and every path of a set in one
 launch (include/dgj2t.h dg_path_* / dg_tget_*). Nothing but field headers is
@@ -229,3 +232,272 @@ def get_by_path_device(paths: PathSet, thrift, in_off, n: int, rec, val_off=None
     s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
     _lib.check(_lib.lib().dg_tget_batch_device(paths.ctx.h, paths.h, root_type, _ptr(thrift), _ptr(in_off), n, _ptr(rec),
                                                _ptr(val_off), _ptr(val_len), s, max_len))
+
+
+# ---------------------------------------------------------------------------
+# MarshalTo ("cutting"): a message written under a wide descriptor re-emitted
+# under a narrower one (thrift/generic/value.go:375-552; dg_cut_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+CUT_MAGIC, CUT_VERSION = 0x31434744, 1  # DG_CUT_MAGIC (include/dgj2t_defs.h)
+CUT_MAX_DEPTH = 64  # DG_CUT_MAX_DEPTH
+CUT_COPY, CUT_MISMATCH, CUT_LIST, CUT_MAP, CUT_STRUCT = 1, 2, 3, 4, 5
+CUT_DROP, CUT_NO_BIT = 0xFFFFFFFF, 0xFF
+CUT_WRITE_DEFAULT, CUT_DISALLOW_UNKNOWN, CUT_NOT_CHECK_REQ = 1, 2, 4
+CUT_OK, CUT_E_READ, CUT_E_TYPE, CUT_E_UNKNOWN, CUT_E_REQUIRED, CUT_E_DEPTH, CUT_E_OVERFLOW = 0, 1, 2, 3, 4, 5, 0xF0
+CUT_ERROR_NAMES = {CUT_OK: None, CUT_E_READ: "ErrRead", CUT_E_TYPE: "ErrDismatchType",
+                   CUT_E_UNKNOWN: "ErrUnknownField", CUT_E_REQUIRED: "ErrMissRequiredField",
+                   CUT_E_DEPTH: "ErrDepth", CUT_E_OVERFLOW: "ErrOverflow"}
+_CUT_HDR, _CUT_NODE, _CUT_FIELD, _CUT_LIT = "<16I", "<6I2Q", "<hBBI", "<hHI"
+_REQUIRED = 2  # thrift.REQUIRED
+
+
+def same_descriptor(a, b) -> bool:
+    """The reference compares descriptor pointers (`to.Elem() == from.Elem()`)
+    and shares its builtin descriptors (thrift/idl.go:540-551); thrift.py's
+    builtin() makes a new object per use. So two descriptors are the same when
+    they are the same Python object, or when both are base types (no struct,
+    key or elem) of equal `type` and `name`."""
+    if a is b:
+        return True
+    if a is None or b is None:
+        return False
+
+    def base(d):
+        return d.struct is None and d.key is None and d.elem is None
+
+    return base(a) and base(b) and a.type == b.type and a.name == b.name
+
+
+def write_empty(td) -> bytes:
+    """BinaryProtocol.WriteEmpty (thrift/binary.go:483-515)."""
+    t = td.type
+    fixed = {2: 1, 3: 1, 6: 2, 8: 4, 10: 8, 4: 8, 11: 4}  # a string: its zero length
+    if t in fixed:
+        return b"\0" * fixed[t]
+    if t in (LIST, SET):
+        return bytes([td.elem.type]) + b"\0\0\0\0"
+    if t == MAP:
+        return bytes([td.key.type, td.elem.type]) + b"\0\0\0\0"
+    if t == STRUCT:
+        return b"\0"  # "to avoid self-cycled type dead loop here, just write empty struct"
+    raise ValueError("invalid type %d" % t)
+
+
+def compile_cut(from_desc, to_desc) -> bytes:
+    """The cut plan dg_cut_create takes (layout: include/dgj2t_defs.h,
+    DG_CUT_MAGIC): the graph of (from, to) descriptor pairs marshalTo can
+    reach, walked once and memoised on (id(from), id(to)), so recursive
+    descriptors terminate. Per pair, as value.go:392-543 decides it: a `to`
+    struct is cut field by field; a `to` list, set or map whose element (and
+    key) descriptors are not the same as `from`'s (same_descriptor: the same
+    object, or base types of equal type and name) is cut entry by entry;
+    everything else is a whole-value copy when the two types are equal and
+    ErrDismatchType, raised when such a value is reached in a message, when
+    they are not.
+
+    Where this differs from the reference:
+      * the same struct descriptor on both sides (value.go:395-397 returns
+        without reading, which desynchronises its reader): ValueError;
+      * `to` is a struct and `from` is not (a nil dereference there):
+        ValueError;
+      * differing root types: ConvError("ErrDismatchType"), as MarshalTo
+        returns it before reading;
+      * a `to` struct with more than 64 tracked fields (StructDescriptor.requires
+        set), or a tracked field with a negative id (RequiresBitmap.Set
+        panics on one): ValueError -- the live mask is one 64-bit word;
+      * more than CUT_MAX_DEPTH cut containers open in a message end it with
+        CUT_E_DEPTH (the reference recurses without limit); nesting inside a
+        skipped or copied value is not counted and keeps SkipType's 1023."""
+    if from_desc.type != to_desc.type:
+        raise ConvError("ErrDismatchType", "to descriptor dismatches from descriptor")
+    nodes, fields, lits, pool = [], [], [], bytearray()
+    memo = {}
+    keep = []  # the descriptors whose id() keys the memo
+    max_unset = 0
+
+    def skip_val(f, t):
+        return (CUT_COPY, t.type) if f.type == t.type else (CUT_MISMATCH, 0)
+
+    def node(f, t) -> int:
+        nonlocal max_unset
+        key = (id(f), id(t))
+        if key in memo:
+            return memo[key]
+        idx = memo[key] = len(nodes)
+        keep.append((f, t))
+        nodes.append(None)
+        tt = t.type
+        row = None
+        if tt == STRUCT:
+            if f is t or (f.struct is not None and f.struct is t.struct):
+                raise ValueError("the same struct descriptor '%s' on both sides of a cut" % t.name)
+            if f.type != STRUCT or f.struct is None or t.struct is None:
+                raise ValueError("'%s' is a struct in the to descriptor and none in the from descriptor" % t.name)
+            tracked = sorted(fid for fid, on in t.struct.requires.items() if on)
+            if len(tracked) > 64:
+                raise ValueError("struct '%s': %d tracked fields (at most 64)" % (t.name, len(tracked)))
+            if tracked and tracked[0] < 0:
+                raise ValueError("struct '%s': tracked field id %d is negative" % (t.name, tracked[0]))
+            bit_of = {fid: k for k, fid in enumerate(tracked)}
+            required, unset = 0, 0
+            lit0 = len(lits)
+            for k, fid in enumerate(tracked):
+                tf = t.struct.field_by_id(fid)
+                if tf.required == _REQUIRED:
+                    required |= 1 << k
+                    lits.append(struct.pack(_CUT_LIT, fid, 0, 0))
+                else:
+                    lit = struct.pack(">Bh", tf.type.type, fid) + write_empty(tf.type)
+                    lits.append(struct.pack(_CUT_LIT, fid, len(lit), len(pool)))
+                    pool.extend(lit)
+                    unset += len(lit)
+            max_unset = max(max_unset, unset)
+            ffs = sorted(f.struct.ids.values(), key=lambda x: x.id)
+            fld0 = len(fields)
+            fields.extend([None] * len(ffs))  # the range stays contiguous while children add theirs
+            for k, ff in enumerate(ffs):
+                tf = t.struct.field_by_id(ff.id)
+                child = CUT_DROP if tf is None else node(ff.type, tf.type)
+                bit = CUT_NO_BIT if tf is None else bit_of.get(ff.id, CUT_NO_BIT)
+                fields[fld0 + k] = struct.pack(_CUT_FIELD, ff.id, ff.type.type, bit, child)
+            row = (CUT_STRUCT, fld0, 0, len(ffs), lit0, len(tracked), (1 << len(tracked)) - 1, required)
+        elif tt in (LIST, SET):
+            if f.type not in (LIST, SET):
+                row = (CUT_MISMATCH, 0)
+            elif same_descriptor(t.elem, f.elem):
+                row = skip_val(f, t)
+            else:
+                row = (CUT_LIST, node(f.elem, t.elem))
+        elif tt == MAP:
+            if f.type != MAP:
+                row = (CUT_MISMATCH, 0)
+            elif same_descriptor(t.elem, f.elem) and same_descriptor(t.key, f.key):
+                row = skip_val(f, t)
+            else:
+                row = (CUT_MAP, node(f.key, t.key), node(f.elem, t.elem))
+        else:
+            row = skip_val(f, t)
+        row = tuple(row) + (0,) * (8 - len(row))
+        nodes[idx] = struct.pack(_CUT_NODE, *row)
+        return idx
+
+    root = node(from_desc, to_desc)
+    off_nodes = 64
+    off_fields = off_nodes + 40 * len(nodes)
+    off_lits = off_fields + 8 * len(fields)
+    off_pool = off_lits + 8 * len(lits)
+    hdr = struct.pack(_CUT_HDR, CUT_MAGIC, CUT_VERSION, off_pool + len(pool), root, len(nodes), off_nodes, len(fields),
+                      off_fields, len(lits), off_lits, off_pool, len(pool), max_unset, 0, 0, 0)
+    return hdr + b"".join(nodes) + b"".join(fields) + b"".join(lits) + bytes(pool)
+
+
+class CutOptions:
+    """thrift/generic Options as marshalTo reads them: WriteDefault,
+    DisallowUnknow, NotCheckRequireNess."""
+    __slots__ = ("write_default", "disallow_unknown", "not_check_requireness")
+
+    def __init__(self, write_default=False, disallow_unknown=False, not_check_requireness=False):
+        self.write_default = bool(write_default)
+        self.disallow_unknown = bool(disallow_unknown)
+        self.not_check_requireness = bool(not_check_requireness)
+
+    def word(self) -> int:
+        return (CUT_WRITE_DEFAULT * self.write_default | CUT_DISALLOW_UNKNOWN * self.disallow_unknown |
+                CUT_NOT_CHECK_REQ * self.not_check_requireness)
+
+
+def _cut_word(opts) -> int:
+    return 0 if opts is None else opts.word() if hasattr(opts, "word") else int(opts)
+
+
+class CutPlan:
+    """A compiled cut plan on one context's device (dg_cut)."""
+
+    def __init__(self, from_desc, to_desc=None, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.blob = from_desc if isinstance(from_desc, (bytes, bytearray)) else compile_cut(from_desc, to_desc)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dg_cut_create(self.ctx.h, bytes(self.blob), len(self.blob), C.byref(h)))
+        self.h = h
+
+    def slot_bound(self, length: int, opts=None) -> int:
+        return int(_lib.lib().dg_cut_slot_bound(self.h, length, _cut_word(opts)))
+
+    def close(self):
+        if self.h:
+            _lib.lib().dg_cut_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class CutResult:
+    """One message: .status (CUT_OK, CUT_E_*), .raw (the cut message, empty
+    unless CUT_OK), .error (None, "ErrRead", "ErrDismatchType",
+    "ErrUnknownField", "ErrMissRequiredField", "ErrDepth"), .aux (the field id
+    of a field-level error, sign-extended to 32 bits as the device stores it)."""
+    __slots__ = ("status", "raw", "error", "aux")
+
+    def __init__(self, ret: int, raw: bytes):
+        self.status, self.aux = int(ret) & 0xFF, int(ret) >> 32
+        self.raw = raw if self.status == CUT_OK else b""
+        self.error = CUT_ERROR_NAMES.get(self.status, "ErrRead")
+
+    def __repr__(self):
+        return "CutResult(status=%d, aux=%d, %d bytes)" % (self.status, self.aux, len(self.raw))
+
+
+def marshal_to_batch(msgs: Sequence[bytes], from_desc, to_desc=None, opts=None,
+                     ctx: Optional[Context] = None) -> List[CutResult]:
+    """Value.MarshalTo for every message of a batch (dg_cut_batch_host):
+    msgs[i], written under from_desc, cut to to_desc. from_desc may be a
+    CutPlan (to_desc is then unused). Descriptor sameness: same_descriptor."""
+    plan = from_desc if isinstance(from_desc, CutPlan) else CutPlan(from_desc, to_desc, ctx)
+    try:
+        n = len(msgs)
+        L = _lib.lib()
+        if n == 0:
+            _lib.check(L.dg_cut_batch_host(plan.ctx.h, plan.h, _cut_word(opts), None, None, 0, None, 0, None, None, None))
+            return []
+        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
+        in_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(lens, out=in_off[1:])
+        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        ret = np.zeros(n, dtype=np.uint64)
+        need = C.c_uint64(0)
+        cap = int(in_off[n]) + 4096
+        while True:
+            out = np.zeros(cap, dtype=np.uint8)
+            rc = L.dg_cut_batch_host(plan.ctx.h, plan.h, _cut_word(opts), arena.ctypes.data, in_off.ctypes.data, n,
+                                     out.ctypes.data, cap, out_off.ctypes.data, ret.ctypes.data, C.byref(need))
+            if rc == -3 and need.value > cap:  # DG_E_NOMEM: the literals outgrew the guess
+                cap = int(need.value)
+                continue
+            _lib.check(rc)
+            break
+        return [CutResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes()) for i in range(n)]
+    finally:
+        if plan is not from_desc:
+            plan.close()
+
+
+def marshal_to_device(plan: CutPlan, thrift, in_off, n: int, out, out_off, out_len, ret, opts=None, stream=None,
+                      max_len: int = 0):
+    """Device-resident batch (dg_cut_batch_device) over torch tensors or raw
+    device pointers: thrift uint8[>= in_off[n] + 16]; in_off int64[n + 1]; out
+    uint8, message i's slot out[out_off[i], out_off[i + 1]) (out_off int64[n +
+    1]; plan.slot_bound gives a size that cannot overflow); out_len int32[n];
+    ret int64[n] (status | aux << 32). out must not alias thrift. Asynchronous
+    on `stream` (a torch stream, a raw stream handle, or None for torch's
+    current stream when `thrift` is a tensor)."""
+    if stream is None and hasattr(thrift, "device"):
+        import torch
+        stream = torch.cuda.current_stream(thrift.device)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    _lib.check(_lib.lib().dg_cut_batch_device(plan.ctx.h, plan.h, _cut_word(opts), _ptr(thrift), _ptr(in_off), n, _ptr(out),
+                                              _ptr(out_off), _ptr(out_len), _ptr(ret), s, max_len))

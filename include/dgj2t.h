@@ -81,6 +81,7 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *   "flat_wrap"   DG_FLAT_WRAP    -1 auto, 0 off: the flat kernel for {"key":{flat}} members of a non-flat root
  *   "tget_spread" DG_TGET_SPREAD  0 auto, 1, 2 or 4: every how-manieth lane of the path-lookup kernel takes a
  *                                 (message, path) pair
+ *   "cut_wave_min" DG_CUT_WAVE_MIN messages at least this long take the wave route of the cut (4096; 0 = all)
  * Unknown names return DG_E_INVALID. Thread-safe (the context lock). */
 int dg_ctx_set_knob(dg_ctx *ctx, const char *name, int64_t value);
 int dg_ctx_get_knob(dg_ctx *ctx, const char *name, int64_t *value);
@@ -542,6 +543,78 @@ int dg_tget_batch_device(dg_ctx *ctx, const dg_path *paths, uint8_t root_type, c
 /* Host buffers, synchronous: thrift[in_off[i], in_off[i+1]), rec n * P. */
 int dg_tget_batch_host(dg_ctx *ctx, const dg_path *paths, uint8_t root_type, const uint8_t *thrift,
                        const uint64_t *in_off, uint64_t n, dg_tget_rec *rec);
+
+/*
+ * cut: batched MarshalTo ("cutting", the reference's thrift/generic
+ * Value.MarshalTo, value.go:375-552): every message, written under a wide
+ * descriptor `from`, is re-emitted under a narrower descriptor `to`. Fields
+ * `to` does not know are dropped at every nesting level, the requiredness of
+ * `to` is enforced, and under DG_CUT_WRITE_DEFAULT the unset default fields of
+ * `to` are written as empty values. A plan (the pair graph compiled by
+ * generic.compile_cut, blob layout in dgj2t_defs.h under DG_CUT_MAGIC) is
+ * validated and uploaded once (DG_E_ARG, text in dg_last_error, for a blob
+ * that breaks the layout), belongs to its context and is read-only after.
+ *
+ * Per message, d_ret[i] = status (bits 0-7) | aux << 32 and d_out_len[i]:
+ *   DG_CUT_OK          out_len bytes in the slot
+ *   DG_CUT_E_READ      meta.ErrRead: a short buffer, an invalid type byte in a
+ *                      field, list or map header, a negative size, skip depth
+ *                      beyond 1023 (a message of 4 GiB or more: aux 0xFFFFFFFF)
+ *   DG_CUT_E_TYPE      meta.ErrDismatchType: a field whose wire type is not the
+ *                      one `from` declares (aux = the field id), or a value
+ *                      whose `from` and `to` types cannot be cut (aux = 0)
+ *   DG_CUT_E_UNKNOWN   meta.ErrUnknownField under DG_CUT_DISALLOW_UNKNOWN, aux
+ *                      = the field id
+ *   DG_CUT_E_REQUIRED  meta.ErrMissRequiredField, aux = the lowest missing id
+ *   DG_CUT_E_OVERFLOW  the slot is too small; out_len = aux = the bytes needed
+ *                      (saturated at 2^32 - 1)
+ *   DG_CUT_E_DEPTH     more than DG_CUT_MAX_DEPTH cut containers open
+ * Field ids in aux are sign-extended to 32 bits. out_len is 0 for every error
+ * but the overflow: the reference returns no bytes on error.
+ *
+ * Deviations from the reference, all stated by generic.compile_cut too: the
+ * same struct descriptor on both sides (value.go:395-397 returns without
+ * reading, which desynchronises its reader) and a `to` struct against a `from`
+ * that is none (a nil dereference there) are refused when the plan is
+ * compiled; a `to` struct with more than 64 tracked fields is refused (one
+ * mask word per frame); the reference recurses without limit where
+ * DG_CUT_E_DEPTH ends a message (the depth inside a skipped or copied value is
+ * not counted: it keeps SkipType's 1023).
+ *
+ * Memory contract. Message i is d_thrift[d_in_off[i], d_in_off[i+1]); the arena
+ * is readable 16 bytes past its last message. Its slot is d_out[d_out_off[i],
+ * d_out_off[i+1]) at any alignment: no byte outside it is written, and on
+ * success no byte at or beyond d_out_off[i] + out_len (neither route rounds a
+ * store up). A message that fails or overflows may leave bytes anywhere in its
+ * own slot. d_out must not alias the input.
+ *
+ * Two routes in one launch sequence: a lane per message (short messages), and
+ * a wave per message for those at least "cut_wave_min" bytes long or nested
+ * beyond the lane route's 8 frames, queued on the device.
+ */
+typedef struct dg_cut dg_cut;
+int dg_cut_create(dg_ctx *ctx, const void *blob, size_t len, dg_cut **out);
+void dg_cut_destroy(dg_cut *p);
+/* The slot size that can never overflow for a message of len bytes: len when
+ * no literal can be written (no DG_CUT_WRITE_DEFAULT, or DG_CUT_NOT_CHECK_REQ,
+ * or a plan without default fields), else len * (1 + U), U = the plan's
+ * largest per-struct literal total (every struct instance costs at least its
+ * STOP byte and adds at most U). A worst case: callers may give less and
+ * rerun the messages that report DG_CUT_E_OVERFLOW, as dg_cut_batch_host does. */
+uint64_t dg_cut_slot_bound(const dg_cut *p, uint64_t len, uint64_t opts);
+/* Device buffers, stream-ordered, async (stream NULL: the context's). opts:
+ * DG_CUT_* bits. max_len: the batch's longest message (0 = unknown), a hint.
+ * n = 0 returns DG_OK and launches nothing. */
+int dg_cut_batch_device(dg_ctx *ctx, const dg_cut *plan, uint64_t opts, const uint8_t *d_thrift,
+                        const uint64_t *d_in_off, uint64_t n, uint8_t *d_out, const uint64_t *d_out_off,
+                        uint32_t *d_out_len, uint64_t *d_ret, void *stream, uint64_t max_len);
+/* Host buffers, synchronous: message i's bytes at out + out_off[i] (out_off
+ * has n + 1 entries; failed messages are empty, ret[i] says why); *out_need =
+ * the total. Slot overflows are rerun once in exact-size slots. DG_E_NOMEM when
+ * out_cap is too small (*out_need is set). */
+int dg_cut_batch_host(dg_ctx *ctx, const dg_cut *plan, uint64_t opts, const uint8_t *thrift, const uint64_t *in_off,
+                      uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
+                      uint64_t *out_need);
 
 /* Timing helper for benchmarks: launch the device batch `iters` times on the
  * context stream bracketed by HIP events; returns total milliseconds of GPU

@@ -170,6 +170,78 @@ typedef struct dg_path_step {
     int64_t val;
 } dg_path_step;
 
+/* cut (batched MarshalTo, include/dgj2t.h dg_cut_*): option bits (the
+ * thrift/generic Options fields marshalTo reads) and per-message statuses */
+#define DG_CUT_WRITE_DEFAULT (1ull << 0)    /* WriteDefault */
+#define DG_CUT_DISALLOW_UNKNOWN (1ull << 1) /* DisallowUnknow */
+#define DG_CUT_NOT_CHECK_REQ (1ull << 2)    /* NotCheckRequireNess */
+#define DG_CUT_OK 0u
+#define DG_CUT_E_READ 1u         /* meta.ErrRead */
+#define DG_CUT_E_TYPE 2u         /* meta.ErrDismatchType */
+#define DG_CUT_E_UNKNOWN 3u      /* meta.ErrUnknownField */
+#define DG_CUT_E_REQUIRED 4u     /* meta.ErrMissRequiredField */
+#define DG_CUT_E_DEPTH 5u        /* more than DG_CUT_MAX_DEPTH cut containers open (no reference counterpart) */
+#define DG_CUT_E_OVERFLOW 0xF0u  /* slot too small (the value of DG_ST_OUT_OVERFLOW) */
+#define DG_CUT_MAX_DEPTH 64u
+
+/* Cut-plan blob (generic.compile_cut): everything little-endian, tables
+ * 8-aligned, the pool last; the device copy has 16 zero bytes after it.
+ *
+ *   offset 0           dg_cut_hdr (64 bytes)
+ *   offset off_nodes   n_nodes x dg_cut_node (40 bytes each)
+ *   offset off_fields  n_fields x dg_cut_field (8 bytes each)
+ *   offset off_lits    n_lits x dg_cut_lit (8 bytes each)
+ *   offset off_pool    pool_len literal bytes
+ *   total_len          = off_pool + pool_len
+ *
+ * A node is one (from, to) descriptor pair; `root` is the pair the messages
+ * start with. By kind:
+ *   DG_CUT_COPY      a = the descriptor's type: SkipType(a), the span copied
+ *   DG_CUT_MISMATCH  ErrDismatchType when a value of this pair is reached
+ *   DG_CUT_LIST      a = the element's node (LIST and SET)
+ *   DG_CUT_MAP       a = the key's node, b = the element's node
+ *   DG_CUT_STRUCT    fields [a, a + n_fields) of the field table, sorted by
+ *                    id, one per field of `from` (an id not among them is
+ *                    unknown); lits [lit0, lit0 + n_lits): one entry per
+ *                    tracked field of `to` (RequiresBitmap bit set), ascending
+ *                    id, entry k = bit k of `tracked`, the mask a struct
+ *                    instance starts with; `required` = the bits whose field is
+ *                    Required. n_lits <= 64.
+ * A field: the wire type `from` declares (another one in the message is
+ * ErrDismatchType), child = the node of the (from, to) field types or
+ * DG_CUT_DROP when `to` lacks the id, bit = the field's bit in the masks or
+ * DG_CUT_NO_BIT. A lit: the field id and, for a field that is not Required,
+ * pool[off, off + len) = its field header + WriteEmpty of its type (what
+ * WriteDefault emits while the bit is still set at STOP); len 0 for Required.
+ * max_unset = the largest total of a struct's lit lengths. */
+#define DG_CUT_MAGIC 0x31434744u /* "DGC1" */
+#define DG_CUT_VERSION 1u
+#define DG_CUT_COPY 1u
+#define DG_CUT_MISMATCH 2u
+#define DG_CUT_LIST 3u
+#define DG_CUT_MAP 4u
+#define DG_CUT_STRUCT 5u
+#define DG_CUT_DROP 0xFFFFFFFFu
+#define DG_CUT_NO_BIT 0xFFu
+typedef struct dg_cut_hdr {
+    uint32_t magic, version, total_len, root, n_nodes, off_nodes, n_fields, off_fields, n_lits, off_lits, off_pool,
+        pool_len, max_unset, pad[3];
+} dg_cut_hdr;
+typedef struct dg_cut_node {
+    uint32_t kind, a, b, n_fields, lit0, n_lits;
+    uint64_t tracked, required;
+} dg_cut_node;
+typedef struct dg_cut_field {
+    int16_t id;
+    uint8_t type, bit;
+    uint32_t child;
+} dg_cut_field;
+typedef struct dg_cut_lit {
+    int16_t id;
+    uint16_t len;
+    uint32_t off;
+} dg_cut_lit;
+
 /* t2j (Thrift binary -> JSON, conv/t2j) option bits: the conv.Options fields
  * conv/t2j/impl.go reads (conv/api.go:52-121) */
 #define DG_T2J_BYTE_AS_UINT8 (1ull << 0)     /* ByteAsUint8 */
