@@ -4,7 +4,7 @@
  * orders a shared buffer across streams, the context, descriptor and
  * per-stream scratch records, the entry guard, the argument records of one
  * batch and the error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host and j2t_pipe use them).
+ * tget_host, cut_host, edit_host and j2t_pipe use them).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -261,6 +261,9 @@ struct Knobs {
     int64_t flat_wrap = -1;     /* the flat kernel's wrapped mode for roots that wrap a flat struct (0: off) */
     int64_t tget_spread = 0;    /* tget: lanes per (message, path) pair, 0 = from the longest message (tget_host.hip) */
     int64_t cut_wave_min = 4096; /* cut: messages at least this long take the wave route (0: all of them); ~1.1 KB x 65 536: 256 / 1024 / 4096 / 16384 -> 29.5 / 44.0 / 227.2 / 227.6 GB/s; ~83 KB x 4 096: lane 23.5, wave 26.5 */
+    int64_t edit_reuse_rec = 0;   /* edit, timing only: 1 = a launch of as many messages as the context's previous edit launch skips the lookup and splices from its records (the same batch and path, or the result is undefined) */
+    int64_t edit_lanes = 4;       /* edit: lanes per message on the splice's lane route, 1, 4 or 16 (anything else: 1); splice alone at 1 / 4 / 16, ~227 B x 65 536: 264 / 300 / 254 GB/s, ~1.1 KB x 65 536: 607 / 882 / 908, ~83 KB x 4 096: 47 / 203 / 690 */
+    int64_t edit_wave_min = 4096; /* edit: outputs at least this long take the splice's wave route (0: all of them); ~1.1 KB x 65 536 at 4 lanes, 256 / 1024 / 4096 / 16384 -> 556 / 502 / 884 / 882 GB/s; ~83 KB x 4 096: lane route 203, wave route 1 407 */
 };
 
 /* one chunk in flight of dg_j2t_pipeline_host (j2t_pipe.hip) */
@@ -303,6 +306,11 @@ struct dg_ctx {
     StreamOrder cut;
     DevArr<uint32_t> cut_list, cut_cnt_buf;
     AltCounters cut_cnt;
+    /* edit (edit_host.hip): the lookup's 2 n records of one batch, ordered
+     * across streams like tget's workspace */
+    StreamOrder edit;
+    DevArr<dg_tget_rec> edit_rec;
+    uint64_t edit_rec_n = 0; /* messages of the launch that filled edit_rec */
     /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB) */
     SharedWs t2j_tok;
     /* t2j deep pass: T2J_DEEP_DEPTH frames per lane (about 100 MB, allocated
@@ -368,6 +376,32 @@ struct dg_desc {
     std::vector<uint8_t> hblob; /* host copy of the blob (launch decisions) */
     size_t side_len = 0;
 };
+
+/* a path set on its context's device (tget_host.hip; an edit owns one) */
+struct dg_path {
+    dg_ctx *ctx;
+    DevArr<uint8_t> d_blob;
+    dg_path_hdr hdr;
+};
+
+/* one batch of messages (device pointers) and where the lookup's records go */
+struct TGetBatch {
+    const uint8_t *src;
+    const uint64_t *in_off;
+    uint64_t n;
+    dg_tget_rec *rec;
+    uint64_t *val_off; /* optional, with val_len */
+    uint32_t *val_len;
+    uint64_t max_len;
+};
+
+/* dg_path_create's checks of a path-set blob (DG_E_ARG with its texts); h =
+ * the blob's header */
+__attribute__((visibility("hidden"))) int dg_i_path_validate(const void *blob, size_t len, dg_path_hdr &h);
+
+/* the lookup of one batch on stream s (ctx mutex held): tget_host.hip */
+__attribute__((visibility("hidden"))) int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type,
+                                                      const TGetBatch &b, hipStream_t s);
 
 /* the callback answers of a batch (dg_cb_tables, dgj2t_defs.h): HTTP-mapping
  * entries (DG_F_HM_SPLIT) and value-mapping entries; all null when absent */

@@ -10,23 +10,6 @@
 
 using namespace dg;
 
-struct dg_path {
-    dg_ctx *ctx;
-    DevArr<uint8_t> d_blob;
-    dg_path_hdr hdr;
-};
-
-/* one batch of messages (device pointers) and where its records go */
-struct TGetBatch {
-    const uint8_t *src;
-    const uint64_t *in_off;
-    uint64_t n;
-    dg_tget_rec *rec;
-    uint64_t *val_off; /* optional, with val_len */
-    uint32_t *val_len;
-    uint64_t max_len;
-};
-
 static const uint64_t TGET_WS = (uint64_t)TG_DEEP_DEPTH * TG_DEEP_LANES * 8;
 
 /* every how-manieth lane takes a (message, path) pair. The t2j lane pass
@@ -49,7 +32,7 @@ static uint32_t tget_spread(const dg_ctx *c, uint64_t max_len)
  * and the deep frames are one per context: a launch on another stream than
  * the previous one waits for it. Launches alternate between the counters and
  * each deep pass zeroes the other one (no memset per launch). */
-static int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const TGetBatch &b, hipStream_t s)
+int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const TGetBatch &b, hipStream_t s)
 {
     const uint64_t n = b.n;
     if (n == 0) return DG_OK;
@@ -101,13 +84,9 @@ static int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const TG
     return DG_OK;
 }
 
-extern "C" {
-
-int dg_path_create(dg_ctx *c, const void *blob, size_t len, dg_path **out)
+int dg_i_path_validate(const void *blob, size_t len, dg_path_hdr &h)
 {
-    if (!c || !blob || !out) return set_err(DG_E_INVALID, "null ctx/blob/out");
     if (len < sizeof(dg_path_hdr)) return set_err(DG_E_ARG, "path blob of %zu bytes: no header", len);
-    dg_path_hdr h;
     memcpy(&h, blob, sizeof h);
     if (h.magic != DG_PATH_MAGIC || h.version != DG_PATH_VERSION)
         return set_err(DG_E_ARG, "path blob: bad magic or version (%08x, %u)", h.magic, h.version);
@@ -140,6 +119,16 @@ int dg_path_create(dg_ctx *c, const void *blob, size_t len, dg_path **out)
             if (!key && st.key_len) return set_err(DG_E_ARG, "path %u step %u: key_len on a keyless step", k, s);
         }
     }
+    return DG_OK;
+}
+
+extern "C" {
+
+int dg_path_create(dg_ctx *c, const void *blob, size_t len, dg_path **out)
+{
+    if (!c || !blob || !out) return set_err(DG_E_INVALID, "null ctx/blob/out");
+    dg_path_hdr h;
+    if (int rc = dg_i_path_validate(blob, len, h)) return rc;
     Entry g(c, true);
     if (g.rc) return g.rc;
     std::unique_ptr<dg_path> ps(new dg_path());

@@ -1,4 +1,6 @@
-"""thrift/generic on the GPU. Batched MarshalTo ("cutting", Value.MarshalTo,
+"""thrift/generic on the GPU. Batched SetByPath / UnsetByPath (the third
+part of this module: EditPlan, set_by_path_batch, unset_by_path_batch,
+edit_device), batched MarshalTo ("cutting", Value.MarshalTo,
 value.go:375-552; the second half of this module: compile_cut, CutPlan,
 marshal_to_batch, marshal_to_device), and
 batched GetByPath over Thrift-binary messages: the reference's
@@ -501,3 +503,191 @@ def marshal_to_device(plan: CutPlan, thrift, in_off, n: int, out, out_off, out_l
     s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
     _lib.check(_lib.lib().dg_cut_batch_device(plan.ctx.h, plan.h, _cut_word(opts), _ptr(thrift), _ptr(in_off), n, _ptr(out),
                                               _ptr(out_off), _ptr(out_len), _ptr(ret), s, max_len))
+
+
+# ---------------------------------------------------------------------------
+# SetByPath / UnsetByPath: one path rewritten in every message of a batch
+# (thrift/generic/value.go:263-333, node.go:825-920, 1009-1127; dg_edit_* in
+# dgj2t.h)
+# ---------------------------------------------------------------------------
+EDIT_SET, EDIT_UNSET = 1, 2  # DG_EDIT_SET / DG_EDIT_UNSET (include/dgj2t_defs.h)
+EDIT_OK, EDIT_NOT_FOUND, EDIT_E_READ, EDIT_E_TYPE, EDIT_E_OVERFLOW = 0, 1, 2, 3, 0xF0
+EDIT_EXISTED = 1 << 8
+EDIT_ERROR_NAMES = {EDIT_OK: None, EDIT_NOT_FOUND: "ErrNotFound", EDIT_E_READ: "ErrRead",
+                    EDIT_E_TYPE: "ErrDismatchType", EDIT_E_OVERFLOW: "ErrOverflow"}
+
+
+class EditPlan:
+    """One edit on one context's device (dg_edit): ONE path of at least one
+    step (a list of Path steps; PathFieldName is resolved through `desc` by
+    compile_paths) and an op, EDIT_SET or EDIT_UNSET. `path` may also be the
+    compiled one-path blob.
+
+    SET replaces the value at the path (its wire type must be the new
+    value's), or, when only the path's last step misses, inserts it at the
+    FRONT of the container: a field header + the value at the struct's first
+    byte, an element after the list header, key + value after the map header,
+    the container's count + 1. UNSET drops the field, element or map entry and
+    writes count - 1; a missing PARENT leaves the message as it is.
+
+    Where this differs from the reference:
+      1. a missing field of a nested struct is inserted at the front of the
+         struct that was searched (the reference inserts it at byte 0 of the
+         root message: searchFieldId returns start 0 on a miss);
+      2. the key of an int-key insert is encoded at the width of the map's own
+         key type (the reference uses the value's type);
+      3. an insert whose val_type is not the list's element / the map's value
+         type is ErrDismatchType (the reference writes a corrupt message);
+      4. unset of an absent map key is ErrNotFound (the reference deletes the
+         map's last entry, and writes count -1 on an empty map);
+      5. keys are matched as get_by_path_batch matches them, its I08 rule
+         included, not by deleteChild's raw compare;
+      6. unset on a parent that is no container is ErrDismatchType (the
+         reference silently does nothing);
+      7. the empty path (`*self = sub`) is refused: ValueError here, DG_E_ARG in
+         the C ABI.
+    SetMany and several paths in one plan are out of scope: apply a second
+    edit to the first one's output."""
+
+    def __init__(self, path, op: int, desc=None, ctx: Optional[Context] = None):
+        self.op = int(op)
+        if isinstance(path, (bytes, bytearray)):
+            self.blob = bytes(path)
+        else:
+            if len(path) == 0:
+                raise ValueError("the empty path is no edit")
+            self.blob = compile_paths([path], desc)
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dg_edit_create(self.ctx.h, self.blob, len(self.blob), self.op, C.byref(h)))
+        self.h = h
+
+    def slot_bound(self, length: int, val_len: int = 0) -> int:
+        """The exact worst case of one message's output (dg_edit_slot_bound)."""
+        return int(_lib.lib().dg_edit_slot_bound(self.h, length, val_len))
+
+    def close(self):
+        if self.h:
+            _lib.lib().dg_edit_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class EditResult:
+    """One message: .status (EDIT_OK, EDIT_NOT_FOUND, EDIT_E_READ, EDIT_E_TYPE),
+    .existed (the path was there: a replace or a delete; False for an insert
+    or an untouched message; set only with EDIT_OK), .raw (the edited message,
+    empty unless EDIT_OK), .error (None, "ErrNotFound", "ErrRead",
+    "ErrDismatchType"), .aux (the wire type a type error met, or the lookup's)."""
+    __slots__ = ("status", "existed", "raw", "error", "aux")
+
+    def __init__(self, ret: int, raw: bytes):
+        self.status, self.aux = int(ret) & 0xFF, int(ret) >> 32
+        self.existed = bool(int(ret) & EDIT_EXISTED)
+        self.raw = raw if self.status == EDIT_OK else b""
+        self.error = EDIT_ERROR_NAMES.get(self.status, "ErrRead")
+
+    def __repr__(self):
+        return "EditResult(status=%d, existed=%s, aux=%d, %d bytes)" % (self.status, self.existed, self.aux,
+                                                                        len(self.raw))
+
+
+def _edit_batch(msgs, plan: EditPlan, values, val_type: int, root_type: int) -> List[EditResult]:
+    n = len(msgs)
+    L = _lib.lib()
+    if n == 0:
+        _lib.check(L.dg_edit_batch_host(plan.ctx.h, plan.h, root_type, None, None, 0, val_type, None, None, 0, None, 0,
+                                        None, None, None))
+        return []
+    lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
+    in_off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(lens, out=in_off[1:])
+    arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+    val = val_off = None
+    val_len = vtotal = 0
+    if values is not None:
+        if isinstance(values, (bytes, bytearray)):
+            val = np.frombuffer(bytes(values) + b"\0" * 16, dtype=np.uint8)
+            val_len = vtotal = len(values)
+        else:
+            if len(values) != n:
+                raise ValueError("%d values for %d messages" % (len(values), n))
+            val_off = np.zeros(n + 1, dtype=np.uint64)
+            np.cumsum(np.fromiter((len(v) for v in values), dtype=np.uint64, count=n), out=val_off[1:])
+            val = np.frombuffer(b"".join(bytes(v) for v in values) + b"\0" * 16, dtype=np.uint8)
+            vtotal = int(val_off[n])
+    out_off = np.zeros(n + 1, dtype=np.uint64)
+    ret = np.zeros(n, dtype=np.uint64)
+    need = C.c_uint64(0)
+    cap = int(in_off[n]) + (vtotal if val_off is not None else 0)  # a guess; the call says what it needs
+    while True:
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        rc = L.dg_edit_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n, val_type,
+                                  None if val is None else val.ctypes.data,
+                                  None if val_off is None else val_off.ctypes.data, val_len, out.ctypes.data, cap,
+                                  out_off.ctypes.data, ret.ctypes.data, C.byref(need))
+        if rc == -3 and need.value > cap:  # DG_E_NOMEM: the inserts outgrew the guess
+            cap = int(need.value)
+            continue
+        _lib.check(rc)
+        break
+    return [EditResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes()) for i in range(n)]
+
+
+def set_by_path_batch(msgs: Sequence[bytes], path, values, val_type: int, desc=None, root_type: int = STRUCT,
+                      ctx: Optional[Context] = None) -> List[EditResult]:
+    """SetByPath for every message of a batch (dg_edit_batch_host): the value
+    at `path` (a list of Path steps, or an EditPlan of op EDIT_SET) becomes
+    `values`, one `bytes` for all messages or a sequence with one entry per
+    message: the value's Thrift-binary bytes, taken as given, of wire type
+    val_type. Semantics and the deviations from the reference: EditPlan."""
+    plan = path if isinstance(path, EditPlan) else EditPlan(path, EDIT_SET, desc, ctx)
+    try:
+        if plan.op != EDIT_SET:
+            raise ValueError("set_by_path_batch needs an EDIT_SET plan")
+        return _edit_batch(msgs, plan, values, val_type, root_type)
+    finally:
+        if plan is not path:
+            plan.close()
+
+
+def unset_by_path_batch(msgs: Sequence[bytes], path, desc=None, root_type: int = STRUCT,
+                        ctx: Optional[Context] = None) -> List[EditResult]:
+    """UnsetByPath for every message of a batch: the field, element or map
+    entry at `path` (a list of Path steps, or an EditPlan of op EDIT_UNSET) is
+    dropped. Semantics and the deviations from the reference: EditPlan."""
+    plan = path if isinstance(path, EditPlan) else EditPlan(path, EDIT_UNSET, desc, ctx)
+    try:
+        if plan.op != EDIT_UNSET:
+            raise ValueError("unset_by_path_batch needs an EDIT_UNSET plan")
+        return _edit_batch(msgs, plan, None, 0, root_type)
+    finally:
+        if plan is not path:
+            plan.close()
+
+
+def edit_device(plan: EditPlan, thrift, in_off, n: int, val_type: int, val, val_off, out, out_off, out_len, ret,
+                root_type: int = STRUCT, val_len: int = 0, stream=None, max_len: int = 0):
+    """Device-resident batch (dg_edit_batch_device) over torch tensors or raw
+    device pointers: thrift uint8[>= in_off[n] + 16]; in_off int64[n + 1]; val
+    uint8 with 16 spare bytes, val_off int64[n + 1] or None (then val[0,
+    val_len) serves every message; with val_off, val_len is the longest value
+    or 0); out uint8, message i's slot out[out_off[i], out_off[i + 1])
+    (plan.slot_bound gives the size that cannot overflow); out_len int32[n];
+    ret int64[n] (status | EDIT_EXISTED | aux << 32). An UNSET plan ignores
+    val_type, val, val_off and val_len. out must not alias thrift. max_len,
+    when given, must not be less than the longest message. Asynchronous on
+    `stream` (a torch stream, a raw stream handle, or None for torch's current
+    stream when `thrift` is a tensor)."""
+    if stream is None and hasattr(thrift, "device"):
+        import torch
+        stream = torch.cuda.current_stream(thrift.device)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    _lib.check(_lib.lib().dg_edit_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n, val_type,
+                                               _ptr(val), _ptr(val_off), val_len, _ptr(out), _ptr(out_off),
+                                               _ptr(out_len), _ptr(ret), s, max_len))

@@ -82,6 +82,11 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *   "tget_spread" DG_TGET_SPREAD  0 auto, 1, 2 or 4: every how-manieth lane of the path-lookup kernel takes a
  *                                 (message, path) pair
  *   "cut_wave_min" DG_CUT_WAVE_MIN messages at least this long take the wave route of the cut (4096; 0 = all)
+ *   "edit_wave_min" DG_EDIT_WAVE_MIN edited messages at least this long take the wave route of the splice (4096; 0 = all)
+ *   "edit_lanes"  DG_EDIT_LANES   lanes per message on the splice's lane route: 1, 4 or 16 (4)
+ *   "edit_reuse_rec" (no env)     timing only: 1 = an edit launch of as many messages as the context's previous
+ *                                 one skips the lookup and splices from its records (tools/edit_bench.py times the
+ *                                 splice alone with it; another batch or path gives undefined results)
  * Unknown names return DG_E_INVALID. Thread-safe (the context lock). */
 int dg_ctx_set_knob(dg_ctx *ctx, const char *name, int64_t value);
 int dg_ctx_get_knob(dg_ctx *ctx, const char *name, int64_t *value);
@@ -615,6 +620,112 @@ int dg_cut_batch_device(dg_ctx *ctx, const dg_cut *plan, uint64_t opts, const ui
 int dg_cut_batch_host(dg_ctx *ctx, const dg_cut *plan, uint64_t opts, const uint8_t *thrift, const uint64_t *in_off,
                       uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret,
                       uint64_t *out_need);
+
+/*
+ * edit: batched SetByPath / UnsetByPath over Thrift-binary messages (the
+ * reference's thrift/generic Value.SetByPath / Node.SetByPath with setNotFound
+ * and replace, value.go:263-299 and node.go:825-920, and UnsetByPath with
+ * deleteChild, value.go:302-333 and node.go:1009-1127). One edit is ONE path of
+ * 1 to DG_TGET_MAX_STEPS steps and one op, applied to every message of a batch:
+ * the path lookup (dg_tget_*) runs on the path without its last step (`parent`)
+ * and on the whole path (`full`), then a splice kernel re-emits each message as
+ * prefix + new bytes + suffix with the container's count patched.
+ *
+ * DG_EDIT_SET (a value of wire type val_type, its bytes taken as given):
+ *   full found          its type must be val_type (else DG_EDIT_E_TYPE, aux =
+ *                       the type found); out = msg[0, start) + value +
+ *                       msg[end, len), DG_EDIT_EXISTED set.
+ *   full missed at its  an insert at the FRONT of the container (the reference's
+ *   last step           TestSetByPath reads the new element back at index 0):
+ *                       FIELD: type(1) id(BE16) value at parent.start, the first
+ *                       byte of the struct that was searched (parent must be
+ *                       found: its status passes through otherwise); INDEX: value
+ *                       after the list header; a key step: key bytes + value after
+ *                       the map header (STRKEY: 4-byte length + bytes; BINKEY: the
+ *                       pool bytes; INTKEY: the key big-endian at the width of the
+ *                       map's key type). The container's big-endian i32 count gets
+ *                       int32(count + 1), wrapping as the reference's does. A
+ *                       val_type that is not the list's element / the map's value
+ *                       type is DG_EDIT_E_TYPE (aux = the header's type).
+ *   full missed earlier DG_EDIT_NOT_FOUND; DG_TGET_E_READ / DG_TGET_E_TYPE of
+ *                       the lookup pass through with its aux.
+ * DG_EDIT_UNSET (the value arguments are ignored):
+ *   parent missed       DG_EDIT_OK, the message copied unchanged (the reference
+ *                       returns nil); parent E_READ / E_TYPE pass through.
+ *   parent found        a STRUCT needs a FIELD step, a LIST or SET an INDEX step,
+ *                       a MAP a key step; anything else is DG_EDIT_E_TYPE (aux =
+ *                       the parent's type). full found: the entry is dropped --
+ *                       [start - 3, end) for a field, [start, end) for an element,
+ *                       [start - key length, end) for a map entry -- the count gets
+ *                       int32(count - 1) and DG_EDIT_EXISTED is set. full missed:
+ *                       DG_EDIT_NOT_FOUND; full E_READ / E_TYPE pass through.
+ * d_ret[i] = status | DG_EDIT_EXISTED | aux << 32; d_out_len[i] = the output
+ * length, 0 on an error, the bytes needed on DG_EDIT_E_OVERFLOW (aux too,
+ * saturated at 2^32 - 1). A message that fails or overflows writes nothing.
+ *
+ * Deviations from the reference:
+ *   1. A missing field of a nested struct: searchFieldId returns start 0 on a
+ *      miss (node.go:302), so SetByPath inserts the new field at byte 0 of the
+ *      ROOT message whatever struct was searched; here it goes to the front of
+ *      the struct that was searched.
+ *   2. The key of an INTKEY insert: setNotFound encodes it with
+ *      path.ToRaw(n.t), the VALUE's type (node.go:879): nil or the wrong width
+ *      unless the two coincide; here the map's own key type gives the width.
+ *   3. An insert into a list or map does not check the element type there and
+ *      leaves a corrupt message; here a differing val_type is DG_EDIT_E_TYPE.
+ *   4. Unset of an absent map key deletes the map's LAST entry there and writes
+ *      count - 1 (-1 on an empty map); here it is DG_EDIT_NOT_FOUND, like the
+ *      other containers.
+ *   5. Keys are matched as the lookup matches them (its I08 rule included), not
+ *      by deleteChild's raw compare.
+ *   6. Unset on a parent that is no container silently does nothing there; here
+ *      it is DG_EDIT_E_TYPE.
+ *   7. The empty path (`*self = sub`) is no edit of a message: dg_edit_create
+ *      refuses it with DG_E_ARG.
+ * SetMany, or several paths in one edit, are out of scope: a second edit is a
+ * second call on the first one's output.
+ *
+ * dg_edit_create takes the DG_PATH_MAGIC blob of dg_path_create with exactly
+ * one path of at least one step (DG_E_ARG otherwise, and for every blob
+ * dg_path_create refuses, with its texts). The handle belongs to its context
+ * and is read-only after creation.
+ */
+typedef struct dg_edit dg_edit;
+int dg_edit_create(dg_ctx *ctx, const void *path_blob, size_t len, uint32_t op, dg_edit **out);
+void dg_edit_destroy(dg_edit *e);
+/* The exact worst case of one message's output: DG_EDIT_UNSET: len;
+ * DG_EDIT_SET: len + val_len + what the path's last step can add (FIELD 3,
+ * INDEX 0, STRKEY 4 + the key's length, BINKEY the key's length, INTKEY 8). */
+uint64_t dg_edit_slot_bound(const dg_edit *e, uint64_t len, uint64_t val_len);
+/* Device buffers, stream-ordered, async (stream NULL: the context's). Messages
+ * and root_type as dg_tget_batch_device (the arena readable 16 bytes past its
+ * end; n * 2 below 2^32). Values: with d_val_off, message i's value is
+ * d_val[d_val_off[i], d_val_off[i+1]) and val_len is the longest value (0 =
+ * unknown), a hint; with d_val_off NULL every message gets d_val[0, val_len).
+ * The value arena is readable 16 bytes past its end.
+ * Message i's slot is d_out[d_out_off[i], d_out_off[i+1]) at any alignment: no
+ * byte outside [d_out_off[i], d_out_off[i] + out_len) is written (no store is
+ * rounded up). d_out must not alias d_thrift. max_len: the batch's longest
+ * message, or 0 for unknown. The launch leaves out a route that no output can
+ * take by the two hints, so a hint that is given must not be too small: a
+ * message longer than it may be left unwritten. n = 0 returns DG_OK and
+ * launches nothing.
+ * The lookup's 2 n records live in a scratch of the context, ordered across
+ * streams like the lookup's own workspace. Two routes: "edit_lanes" lanes per
+ * message (1, 4 or 16), and a wave per message for outputs at least
+ * "edit_wave_min" bytes long. */
+int dg_edit_batch_device(dg_ctx *ctx, const dg_edit *e, uint8_t root_type, const uint8_t *d_thrift,
+                         const uint64_t *d_in_off, uint64_t n, uint8_t val_type, const uint8_t *d_val,
+                         const uint64_t *d_val_off, uint64_t val_len, uint8_t *d_out, const uint64_t *d_out_off,
+                         uint32_t *d_out_len, uint64_t *d_ret, void *stream, uint64_t max_len);
+/* Host buffers, synchronous: val / val_off as above (host memory; no spare
+ * bytes needed); message i's bytes at out + out_off[i] (out_off has n + 1
+ * entries; failed messages are empty, ret[i] says why); *out_need = the total.
+ * Every slot has its exact bound, so nothing is rerun. DG_E_NOMEM when out_cap
+ * is too small (*out_need is set). */
+int dg_edit_batch_host(dg_ctx *ctx, const dg_edit *e, uint8_t root_type, const uint8_t *thrift, const uint64_t *in_off,
+                       uint64_t n, uint8_t val_type, const uint8_t *val, const uint64_t *val_off, uint64_t val_len,
+                       uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret, uint64_t *out_need);
 
 /* Timing helper for benchmarks: launch the device batch `iters` times on the
  * context stream bracketed by HIP events; returns total milliseconds of GPU

@@ -242,6 +242,18 @@ typedef struct dg_cut_lit {
     uint32_t off;
 } dg_cut_lit;
 
+/* edit (batched SetByPath / UnsetByPath, include/dgj2t.h dg_edit_*): the two
+ * ops and the per-message return word, status (bits 0-7, tget's numbers) |
+ * DG_EDIT_EXISTED | aux << 32 */
+#define DG_EDIT_SET 1u
+#define DG_EDIT_UNSET 2u
+#define DG_EDIT_OK 0u
+#define DG_EDIT_NOT_FOUND 1u      /* meta.ErrNotFound */
+#define DG_EDIT_E_READ 2u         /* meta.ErrRead */
+#define DG_EDIT_E_TYPE 3u         /* meta.ErrDismatchType */
+#define DG_EDIT_E_OVERFLOW 0xF0u  /* slot too small (the value of DG_ST_OUT_OVERFLOW) */
+#define DG_EDIT_EXISTED (1ull << 8) /* the path was there: a replace or a delete, not an insert or a no-op */
+
 /* t2j (Thrift binary -> JSON, conv/t2j) option bits: the conv.Options fields
  * conv/t2j/impl.go reads (conv/api.go:52-121) */
 #define DG_T2J_BYTE_AS_UINT8 (1ull << 0)     /* ByteAsUint8 */
