@@ -24,7 +24,8 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_t2j_batch_device_cb", "dg_t2j_batch_host_cb",
            "dg_path_create", "dg_path_destroy", "dg_path_count", "dg_tget_batch_device", "dg_tget_batch_host",
            "dg_cut_create", "dg_cut_destroy", "dg_cut_slot_bound", "dg_cut_batch_device", "dg_cut_batch_host",
-           "dg_edit_create", "dg_edit_destroy", "dg_edit_slot_bound", "dg_edit_batch_device", "dg_edit_batch_host"]
+           "dg_edit_create", "dg_edit_destroy", "dg_edit_slot_bound", "dg_edit_batch_device", "dg_edit_batch_host",
+           "dg_kids_batch_device", "dg_kids_batch_host"]
 
 _lib = None
 
@@ -120,6 +121,8 @@ def lib() -> C.CDLL:
         "dg_edit_slot_bound": (u64, [vp, u64, u64]),
         "dg_edit_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, u64]),
         "dg_edit_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, C.c_uint8, vp, vp, u64, vp, u64, vp, vp, P64]),
+        "dg_kids_batch_device": (i32, [vp, vp, C.c_uint8, u32, vp, vp, u64, vp, vp, vp, u64, vp, u64]),
+        "dg_kids_batch_host": (i32, [vp, vp, C.c_uint8, u32, vp, vp, u64, vp, vp, vp, u64, P64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -4,7 +4,7 @@
  * orders a shared buffer across streams, the context, descriptor and
  * per-stream scratch records, the entry guard, the argument records of one
  * batch and the error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host, edit_host and j2t_pipe use them).
+ * tget_host, cut_host, edit_host, kids_host and j2t_pipe use them).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -264,6 +264,8 @@ struct Knobs {
     int64_t edit_reuse_rec = 0;   /* edit, timing only: 1 = a launch of as many messages as the context's previous edit launch skips the lookup and splices from its records (the same batch and path, or the result is undefined) */
     int64_t edit_lanes = 4;       /* edit: lanes per message on the splice's lane route, 1, 4 or 16 (anything else: 1); splice alone at 1 / 4 / 16, ~227 B x 65 536: 264 / 300 / 254 GB/s, ~1.1 KB x 65 536: 607 / 882 / 908, ~83 KB x 4 096: 47 / 203 / 690 */
     int64_t edit_wave_min = 4096; /* edit: outputs at least this long take the splice's wave route (0: all of them); ~1.1 KB x 65 536 at 4 lanes, 256 / 1024 / 4096 / 16384 -> 556 / 502 / 884 / 882 GB/s; ~83 KB x 4 096: lane route 203, wave route 1 407 */
+    int64_t kids_wide_min = 256;  /* kids: a list, set or map node of fixed-size entries with at least this many children is emitted by the record-parallel kernel (0: never); emit pass, 16 384 x list<i64> of 64 / 128 / 256 / 1024, lane route 0.107 / 0.159 / 0.261 / 1.314 ms, wide route 0.264 / 0.270 / 0.278 / 0.350 */
+    int64_t kids_no_scan = 0;     /* kids, timing only: 1 = a call leaves the scan out (rec_off is not written) */
 };
 
 /* one chunk in flight of dg_j2t_pipeline_host (j2t_pipe.hip) */
@@ -311,6 +313,13 @@ struct dg_ctx {
     StreamOrder edit;
     DevArr<dg_tget_rec> edit_rec;
     uint64_t edit_rec_n = 0; /* messages of the launch that filled edit_rec */
+    /* kids (kids_host.hip): the deep pass's frames (32 MB, allocated by the
+     * first call), the deep and wide queues (n entries each), the two
+     * alternating counter sets {deep, wide} and the scan's tile sums */
+    SharedWs kids;
+    DevArr<uint32_t> kids_list, kids_cnt_buf;
+    AltCounters kids_cnt;
+    DevArr<uint64_t> kids_sums;
     /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB) */
     SharedWs t2j_tok;
     /* t2j deep pass: T2J_DEEP_DEPTH frames per lane (about 100 MB, allocated

@@ -122,6 +122,8 @@ static int64_t *knob_ref(dg_ctx *c, const char *name)
     if (!strcmp(name, "edit_wave_min")) return &K.edit_wave_min;
     if (!strcmp(name, "edit_reuse_rec")) return &K.edit_reuse_rec;
     if (!strcmp(name, "edit_lanes")) return &K.edit_lanes;
+    if (!strcmp(name, "kids_wide_min")) return &K.kids_wide_min;
+    if (!strcmp(name, "kids_no_scan")) return &K.kids_no_scan;
     return nullptr;
 }
 
@@ -157,7 +159,8 @@ int dg_ctx_create(int device, dg_ctx **out)
         {"DG_SMALL_MPW", "small_mpw"}, {"DG_LIST_BLOCKS", "list_blocks"}, {"DG_T2J_SPREAD", "t2j_spread"},
         {"DG_T2J_WAVE_MIN", "t2j_wave_min"}, {"DG_T2J_OVERLAP", "t2j_overlap"}, {"DG_FLAT_WRAP", "flat_wrap"},
         {"DG_TGET_SPREAD", "tget_spread"}, {"DG_CUT_WAVE_MIN", "cut_wave_min"},
-        {"DG_EDIT_WAVE_MIN", "edit_wave_min"}, {"DG_EDIT_LANES", "edit_lanes"}};
+        {"DG_EDIT_WAVE_MIN", "edit_wave_min"}, {"DG_EDIT_LANES", "edit_lanes"},
+        {"DG_KIDS_WIDE_MIN", "kids_wide_min"}};
     for (const auto &e : envk) {
         const char *v = getenv(e.env);
         if (v && *v) *knob_ref(c.get(), e.name) = strtoll(v, nullptr, 10);

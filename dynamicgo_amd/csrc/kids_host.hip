@@ -1,0 +1,158 @@
+/*
+ * kids_host.hip — the C ABI of batched Children (include/dgj2t.h dg_kids_*; the
+ * reference's thrift/generic Node.Children behind GetByPath). Kernels:
+ * kids_device.h, kids_kern.hip.
+ */
+#include <string.h>
+
+#include "host_internal.h"
+#include "kids_device.h"
+
+using namespace dg;
+
+static const uint64_t KIDS_WS = (uint64_t)2 * KD_DEEP_DEPTH * KD_DEEP_LANES * 8;
+
+/* one batch (device pointers) */
+struct KidsBatch {
+    const uint8_t *src;
+    const uint64_t *in_off;
+    uint64_t n;
+    dg_kids_head *head;
+    uint64_t *rec_off;
+    dg_kid_rec *recs;
+    uint64_t rec_cap;
+};
+
+/* one batch on stream s (ctx mutex held): count pass -> scan -> emit pass,
+ * each pass followed by its deep pass, the emit pass by the wide kernel. The
+ * queues, the two counter sets (alternating per pass; a deep pass zeroes the
+ * other set), the tile sums and the deep frames are one per context: a launch
+ * on another stream than the previous one waits for it. */
+static int kids_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t flags, const KidsBatch &b, hipStream_t s)
+{
+    const uint64_t n = b.n;
+    if (n == 0) return DG_OK;
+    if (!b.src || !b.in_off || !b.head || !b.rec_off) return set_err(DG_E_INVALID, "null buffer");
+    if (((uintptr_t)b.head & 15) || ((uintptr_t)b.recs & 15) || ((uintptr_t)b.rec_off & 7))
+        return set_err(DG_E_INVALID, "heads or records not 16-byte aligned"); /* 16-byte stores */
+    if (n > 0xFFFFFFFFull) return set_err(DG_E_INVALID, "batch of %llu messages", (unsigned long long)n);
+    if (flags & ~(DG_KIDS_F_RECURSE | DG_KIDS_F_COUNTED)) return set_err(DG_E_INVALID, "unknown flags %x", flags);
+    int rc;
+    if (!c->kids.ws) {
+        if ((rc = c->kids.ws.alloc(KIDS_WS)) || (rc = c->kids_cnt_buf.alloc(4))) return rc;
+        HIPCHK(hipMemset(c->kids_cnt_buf, 0, 16));
+        HIPCHK(hipDeviceSynchronize()); /* before a non-blocking stream counts on it */
+        c->kids_cnt.set[0] = c->kids_cnt_buf;
+        c->kids_cnt.set[1] = c->kids_cnt_buf + 2;
+        c->kids_cnt.bytes = 8;
+    }
+    const uint64_t tiles = (n + KD_SCAN_TILE - 1) / KD_SCAN_TILE;
+    if (c->kids_list.cap < 2 * n || c->kids_sums.cap < tiles) { /* the previous launch may still use the old ones */
+        HIPCHK(c->kids.wait_host());
+        if ((rc = c->kids_list.grow(2 * n)) || (rc = c->kids_sums.grow(tiles))) return rc;
+    }
+    HIPCHK(c->kids.acquire(s));
+    KDParams A;
+    memset(&A, 0, sizeof A);
+    A.tg.src = b.src, A.tg.in_off = b.in_off, A.tg.root_type = root_type;
+    A.tg.blob = ps->d_blob, A.tg.off_steps = ps->hdr.off_steps, A.tg.off_pool = ps->hdr.off_pool;
+    A.n = n;
+    A.n_steps = ps->hdr.n_steps; /* one path: all the steps are its own */
+    A.recurse = flags & DG_KIDS_F_RECURSE ? 1u : 0u;
+    A.head = b.head, A.rec_off = b.rec_off, A.recs = b.recs, A.rec_cap = b.rec_cap;
+    A.wide_min = c->knobs.kids_wide_min < 0 ? 0 : (uint64_t)c->knobs.kids_wide_min;
+    A.deep_list = c->kids_list, A.wide_list = c->kids_list + n;
+    A.ws = (uint64_t *)(void *)c->kids.ws;
+    A.stats = c->d_stats;
+    hipError_t e = hipSuccess;
+    if (!(flags & DG_KIDS_F_COUNTED)) {
+        A.cnt = c->kids_cnt.mine(), A.reset = c->kids_cnt.other();
+        launch_kids_count(s, A);
+        e = hipGetLastError();
+        c->kids_cnt.finish(e == hipSuccess, s);
+        if (e == hipSuccess && c->knobs.kids_no_scan != 1) { /* the knob: time the count pass alone */
+            launch_kids_scan(s, A, c->kids_sums);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess && b.recs) {
+        A.cnt = c->kids_cnt.mine(), A.reset = c->kids_cnt.other();
+        launch_kids_emit(s, A, (uint32_t)std::max(c->n_cu, 1) * 4u);
+        e = hipGetLastError();
+        c->kids_cnt.finish(e == hipSuccess, s);
+    }
+    HIPCHK(c->kids.publish(s));
+    if (e != hipSuccess) return set_err(DG_E_HIP, "kids launch: %s", hipGetErrorString(e));
+    return DG_OK;
+}
+
+static int kids_args(const dg_ctx *c, const dg_path *ps)
+{
+    if (!c || !ps || ps->ctx != c) return set_err(DG_E_INVALID, "null ctx/path, or a path of another context");
+    if (ps->hdr.n_paths != 1) return set_err(DG_E_ARG, "children: %u paths (exactly 1)", ps->hdr.n_paths);
+    return DG_OK;
+}
+
+extern "C" {
+
+int dg_kids_batch_device(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t flags, const uint8_t *d_thrift,
+                         const uint64_t *d_in_off, uint64_t n, dg_kids_head *d_head, uint64_t *d_rec_off,
+                         dg_kid_rec *d_recs, uint64_t rec_cap, void *stream, uint64_t max_len)
+{
+    if (int rc = kids_args(c, ps)) return rc;
+    (void)max_len; /* one lane route at every length today */
+    Entry g(c, true, stream);
+    if (g.rc) return g.rc;
+    return kids_launch(c, ps, root_type, flags, KidsBatch{d_thrift, d_in_off, n, d_head, d_rec_off, d_recs, rec_cap}, g.s);
+}
+
+int dg_kids_batch_host(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t flags, const uint8_t *thrift,
+                       const uint64_t *in_off, uint64_t n, dg_kids_head *head, uint64_t *rec_off, dg_kid_rec *recs,
+                       uint64_t rec_cap, uint64_t *need)
+{
+    if (int rc = kids_args(c, ps)) return rc;
+    if (flags & DG_KIDS_F_COUNTED) return set_err(DG_E_INVALID, "DG_KIDS_F_COUNTED is the device entry's");
+    if (n == 0) {
+        if (rec_off) rec_off[0] = 0;
+        if (need) *need = 0;
+        return DG_OK;
+    }
+    if (!thrift || !in_off || !head || !rec_off) return set_err(DG_E_INVALID, "null buffer");
+    std::vector<uint64_t> io(n + 1);
+    const uint64_t base = in_off[0];
+    for (uint64_t i = 0; i <= n; i++) {
+        if (in_off[i] < base || (i && in_off[i] < in_off[i - 1])) return set_err(DG_E_INVALID, "in_off not ascending");
+        io[i] = in_off[i] - base;
+    }
+    const uint64_t total = io[n];
+    Entry g(c, true);
+    if (g.rc) return g.rc;
+    const hipStream_t s = g.s;
+    int rc;
+    if ((rc = c->d_json.grow(total + 64)) || (rc = c->d_in_off.grow(n + 1)) || (rc = c->d_aux.grow(2 * n + 2)) ||
+        (rc = c->d_ret.grow(n + 1)))
+        return rc;
+    if (total) HIPCHK(hipMemcpyAsync(c->d_json, thrift + base, total, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c->d_json + total, 0, 64, s));
+    HIPCHK(hipMemcpyAsync(c->d_in_off, io.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s)); /* io is a local */
+    dg_kids_head *d_head = (dg_kids_head *)(void *)c->d_aux.p;
+    KidsBatch b{c->d_json, c->d_in_off, n, d_head, c->d_ret, nullptr, 0};
+    if ((rc = kids_launch(c, ps, root_type, flags, b, s))) return rc; /* count and scan */
+    HIPCHK(hipMemcpyAsync(rec_off, c->d_ret, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(head, d_head, n * sizeof(dg_kids_head), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const uint64_t want = rec_off[n];
+    if (need) *need = want;
+    if (!recs && !rec_cap) return DG_OK; /* sizing */
+    if (want > rec_cap || (!recs && want)) return set_err(DG_E_NOMEM, "children need %llu records", (unsigned long long)want);
+    if (!want) return DG_OK;
+    if ((rc = c->d_out.grow(want * sizeof(dg_kid_rec) + 64))) return rc;
+    b.recs = (dg_kid_rec *)(void *)c->d_out.p, b.rec_cap = want;
+    if ((rc = kids_launch(c, ps, root_type, flags | DG_KIDS_F_COUNTED, b, s))) return rc;
+    HIPCHK(hipMemcpyAsync(recs, c->d_out, want * sizeof(dg_kid_rec), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DG_OK;
+}
+
+}  // extern "C"

@@ -188,13 +188,16 @@ TGI uint32_t tg_value(const uint8_t *b, uint64_t len, uint64_t &p, uint32_t t, b
     return TG_R_FAIL; /* default: errInvalidDataSize */
 }
 
-/* SkipType(t) at b[p] (w = the window loaded at p - k) */
+/* SkipType(t) at b[p] (w = the window loaded at p - k). sp0: the value sits
+ * inside sp0 containers that a caller's own skip has open (kids_device.h): its
+ * depth budget is MaxSkipDepth - sp0 and its frames start at level sp0. */
 template <class FR>
-TGI uint32_t tg_skip(const uint8_t *b, uint64_t len, uint64_t &p, uint32_t t, const FR &fr, const TGWin &w0, uint32_t k0)
+TGI uint32_t tg_skip(const uint8_t *b, uint64_t len, uint64_t &p, uint32_t t, const FR &fr, const TGWin &w0, uint32_t k0,
+                     uint32_t sp0 = 0)
 {
-    uint32_t sp = 0;
+    uint32_t sp = sp0;
     uint32_t r = tg_value(b, len, p, t, false, sp, fr, w0, k0);
-    while (r == TG_R_OK && sp) {
+    while (r == TG_R_OK && sp > sp0) {
         const uint64_t f = fr.at(sp - 1);
         if (!(f >> 48)) { /* a struct: the next field header */
             if (p + 1 > len) return TG_R_FAIL;
@@ -254,9 +257,11 @@ TGI bool tg_map_begin(const uint8_t *b, uint64_t len, uint64_t &p, uint32_t &kt,
     return true;
 }
 
-/* path `path` of the set on the message b[0, len) */
+/* path `path` of the set on the message b[0, len), up to where its last step
+ * lands: DG_TGET_OK = a value of wire type `type` starts at `start` (nothing of
+ * it is read), step = the path's length; anything else is the lookup's result */
 template <class FR>
-TGI TGRes tg_walk(const TGParams &A, const uint8_t *b, uint64_t len, uint32_t path, const FR &fr)
+TGI TGRes tg_seek(const TGParams &A, const uint8_t *b, uint64_t len, uint32_t path, const FR &fr)
 {
     if (len > 0xFFFFFFFFull) return tg_res(DG_TGET_E_READ, 0, 0, 0, 0, 0xFFFFFFFFull);
     const dg_path_ent pe = ((const dg_path_ent *)(const void *)(A.blob + sizeof(dg_path_hdr)))[path];
@@ -355,10 +360,21 @@ TGI TGRes tg_walk(const TGParams &A, const uint8_t *b, uint64_t len, uint32_t pa
             tt = vt;
         }
     }
-    const uint32_t r = tg_skip(b, len, p, tt, fr, tg_ld(b + p), 0);
-    if (r == TG_R_DEEP) return tg_res(TG_ST_DEEP, pe.count);
-    if (r) return tg_res(DG_TGET_E_READ, pe.count);
-    return tg_res(DG_TGET_OK, pe.count, tt, start, p);
+    return tg_res(DG_TGET_OK, pe.count, tt, start, start);
+}
+
+/* path `path` of the set on the message b[0, len): the lookup, then the skip
+ * that finds the value's end */
+template <class FR>
+TGI TGRes tg_walk(const TGParams &A, const uint8_t *b, uint64_t len, uint32_t path, const FR &fr)
+{
+    const TGRes at = tg_seek(A, b, len, path, fr);
+    if (at.status != DG_TGET_OK) return at;
+    uint64_t p = at.start;
+    const uint32_t r = tg_skip(b, len, p, at.type, fr, tg_ld(b + p), 0);
+    if (r == TG_R_DEEP) return tg_res(TG_ST_DEEP, at.step);
+    if (r) return tg_res(DG_TGET_E_READ, at.step);
+    return tg_res(DG_TGET_OK, at.step, at.type, at.start, p);
 }
 
 /* pair q's record (one 16-byte store) and its packing entries */

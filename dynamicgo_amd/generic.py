@@ -1,4 +1,6 @@
-"""thrift/generic on the GPU. Batched SetByPath / UnsetByPath (the third
+"""thrift/generic on the GPU. Batched Children (the fourth part of this
+module: children_batch, children_records, children_device), batched
+SetByPath / UnsetByPath (the third
 part of this module: EditPlan, set_by_path_batch, unset_by_path_batch,
 edit_device), batched MarshalTo ("cutting", Value.MarshalTo,
 value.go:375-552; the second half of this module: compile_cut, CutPlan,
@@ -691,3 +693,141 @@ def edit_device(plan: EditPlan, thrift, in_off, n: int, val_type: int, val, val_
     _lib.check(_lib.lib().dg_edit_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n, val_type,
                                                _ptr(val), _ptr(val_off), val_len, _ptr(out), _ptr(out_off),
                                                _ptr(out_len), _ptr(ret), s, max_len))
+
+
+# ---------------------------------------------------------------------------
+# Children: the table of a node's children, or its whole subtree, for every
+# message of a batch (thrift/generic/node.go:1133-1154, path.go:796-836,
+# 1121-1248; dg_kids_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+KIDS_E_UNSUPPORTED, KIDS_E_OVERFLOW = 4, 0xF0  # DG_KIDS_E_* (include/dgj2t_defs.h)
+KIDS_F_RECURSE, KIDS_F_COUNTED = 1, 2
+KIDS_NO_PARENT = 0xFFFFFFFF
+KIDS_ERROR_NAMES = dict(ERROR_NAMES)
+KIDS_ERROR_NAMES.update({KIDS_E_UNSUPPORTED: "ErrUnsupportedType", KIDS_E_OVERFLOW: "ErrOverflow"})
+KIDS_REC_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4"), ("key_start", "<u4"), ("parent", "<u4"), ("key", "<i8"),
+                           ("type", "u1"), ("kind", "u1"), ("depth", "<u2"), ("n_desc", "<u4")])  # dg_kid_rec
+KIDS_HEAD_DTYPE = np.dtype([("count", "<u4"), ("direct", "<u4"), ("start", "<u4"), ("type", "u1"), ("key_type", "u1"),
+                            ("elem_type", "u1"), ("status", "u1")])  # dg_kids_head
+
+
+class Child:
+    """One child: .path (the step that reaches it from its parent, built by
+    PathFieldId / PathIndex / PathIntKey, or PathStrKey / PathBinKey over the
+    key's bytes in the message), .type (wire type), .start / .end (the value's
+    span in the message), .raw, .parent (index
+    of the enclosing child in the message's list, None for a direct child),
+    .depth (1 = direct), .n_desc (children below it in the list)."""
+    __slots__ = ("path", "type", "start", "end", "raw", "parent", "depth", "n_desc")
+
+    def __init__(self, rec, msg: bytes):
+        kind, key, ks = int(rec["kind"]), int(rec["key"]), int(rec["key_start"])
+        if kind == PS_FIELD:
+            self.path = PathFieldId(key)
+        elif kind == PS_INDEX:
+            self.path = PathIndex(key)
+        elif kind == PS_INTKEY:
+            self.path = PathIntKey(key)
+        elif kind == PS_STRKEY:
+            self.path = PathStrKey(msg[ks + 4:ks + 4 + key])
+        else:
+            self.path = PathBinKey(msg[ks:ks + key])
+        self.type, self.start, self.end = int(rec["type"]), int(rec["start"]), int(rec["end"])
+        self.raw = msg[self.start:self.end]
+        self.parent = None if int(rec["parent"]) == KIDS_NO_PARENT else int(rec["parent"])
+        self.depth, self.n_desc = int(rec["depth"]), int(rec["n_desc"])
+
+    def __repr__(self):
+        return "Child(%r, type=%d, span=[%d,%d), depth=%d)" % (self.path, self.type, self.start, self.end, self.depth)
+
+
+class ChildrenResult:
+    """One message: .status (OK / NOT_FOUND / E_READ / E_TYPE /
+    KIDS_E_UNSUPPORTED), .error (None, "ErrNotFound", "ErrRead",
+    "ErrDismatchType", "ErrUnsupportedType"), the node's .type / .key_type /
+    .elem_type, .direct (its own children: Node.Len of a list, set or map; the
+    failing step when the status is not OK), .start, .children (a list of
+    Child in wire order, preorder in recursive mode; empty unless OK)."""
+    __slots__ = ("status", "error", "type", "key_type", "elem_type", "direct", "start", "children")
+
+    def __init__(self, head, recs, msg: bytes):
+        self.status = int(head["status"])
+        self.error = KIDS_ERROR_NAMES.get(self.status, "ErrRead")
+        self.type, self.key_type, self.elem_type = int(head["type"]), int(head["key_type"]), int(head["elem_type"])
+        self.direct, self.start = int(head["direct"]), int(head["start"])
+        self.children = [Child(r, msg) for r in recs]
+
+    def __repr__(self):
+        return "ChildrenResult(status=%d, type=%d, %d children)" % (self.status, self.type, len(self.children))
+
+
+def _one_path(path, desc, ctx):
+    return path if isinstance(path, PathSet) else PathSet([list(path)], desc, ctx)
+
+
+def children_records(msgs: Sequence[bytes], path=(), recurse: bool = False, desc=None, root_type: int = STRUCT,
+                     ctx: Optional[Context] = None, count_only: bool = False):
+    """(head, rec_off, recs) of dg_kids_batch_host: KIDS_HEAD_DTYPE[n],
+    uint64[n + 1] and KIDS_REC_DTYPE[rec_off[n]]; message i's records are
+    recs[rec_off[i]:rec_off[i + 1]]. count_only stops after the count (recs is
+    empty): head["direct"] is batched Node.Len."""
+    ps = _one_path(path, desc, ctx)
+    try:
+        n = len(msgs)
+        L = _lib.lib()
+        head = np.zeros(n, dtype=KIDS_HEAD_DTYPE)
+        rec_off = np.zeros(n + 1, dtype=np.uint64)
+        flags = KIDS_F_RECURSE if recurse else 0
+        need = C.c_uint64(0)
+        if n == 0:
+            _lib.check(L.dg_kids_batch_host(ps.ctx.h, ps.h, root_type, flags, None, None, 0, None, rec_off.ctypes.data, None,
+                                            0, C.byref(need)))
+            return head, rec_off, np.zeros(0, dtype=KIDS_REC_DTYPE)
+        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
+        in_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(lens, out=in_off[1:])
+        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        cap = 0 if count_only else int(in_off[n]) // 8 + 64  # a guess; the call says what it needs
+        while True:
+            recs = np.zeros(cap, dtype=KIDS_REC_DTYPE)
+            rc = L.dg_kids_batch_host(ps.ctx.h, ps.h, root_type, flags, arena.ctypes.data, in_off.ctypes.data, n,
+                                      head.ctypes.data, rec_off.ctypes.data, recs.ctypes.data if cap else None, cap,
+                                      C.byref(need))
+            if rc == -3 and need.value > cap and not count_only:  # DG_E_NOMEM
+                cap = int(need.value)
+                continue
+            _lib.check(rc)
+            break
+        return head, rec_off, recs[:0 if count_only else int(rec_off[n])]
+    finally:
+        if ps is not path:
+            ps.close()
+
+
+def children_batch(msgs: Sequence[bytes], path=(), recurse: bool = False, desc=None, root_type: int = STRUCT,
+                   ctx: Optional[Context] = None) -> List[ChildrenResult]:
+    """Node.Children for every message of a batch: the children of the node at
+    the end of `path` (a list of Path steps, () for the message's root, or a
+    PathSet of one path), or with recurse the whole subtree below it in
+    preorder. PathFieldName steps are resolved through `desc`."""
+    head, rec_off, recs = children_records(msgs, path, recurse, desc, root_type, ctx)
+    return [ChildrenResult(head[i], recs[int(rec_off[i]):int(rec_off[i + 1])], msgs[i]) for i in range(len(msgs))]
+
+
+def children_device(pathset: PathSet, thrift, in_off, n: int, head, rec_off, recs, rec_cap: int, recurse: bool = False,
+                    counted: bool = False, root_type: int = STRUCT, stream=None, max_len: int = 0):
+    """Device-resident batch (dg_kids_batch_device) over torch tensors or raw
+    device pointers: thrift uint8[>= in_off[n] + 16]; in_off int64[n + 1]; head
+    n 16-byte heads (e.g. an int32 tensor of shape (n, 4)); rec_off int64[n +
+    1]; recs rec_cap 32-byte records (e.g. int32 of shape (rec_cap, 8)) or None
+    to stop after the count; counted: head / rec_off come from an earlier call
+    with the same batch, path and mode. Asynchronous on `stream` (a torch
+    stream, a raw stream handle, or None for torch's current stream when
+    `thrift` is a tensor)."""
+    if stream is None and hasattr(thrift, "device"):
+        import torch
+        stream = torch.cuda.current_stream(thrift.device)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    flags = (KIDS_F_RECURSE if recurse else 0) | (KIDS_F_COUNTED if counted else 0)
+    _lib.check(_lib.lib().dg_kids_batch_device(pathset.ctx.h, pathset.h, root_type, flags, _ptr(thrift), _ptr(in_off), n,
+                                               _ptr(head), _ptr(rec_off), _ptr(recs), rec_cap, s, max_len))

@@ -65,7 +65,8 @@ void *dg_ctx_stream(dg_ctx *ctx);
 int dg_ctx_stats(dg_ctx *ctx, uint64_t *bails, uint64_t *deeps, int reset);
 
 /* Diagnostics: the context's n (<= 16) raw device counters: [0] bails, [1]
- * deep redos, [2..11] wave-kernel phase cycles in a -DDG_WPROF build. */
+ * deep redos, [2..11] wave-kernel phase cycles in a -DDG_WPROF build, [12]
+ * messages the deep passes of dg_kids_* reran (count and emit pass each). */
 int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
 
 /* Routing knobs (no reference counterpart; testing and tuning). They are read
@@ -84,6 +85,10 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *   "cut_wave_min" DG_CUT_WAVE_MIN messages at least this long take the wave route of the cut (4096; 0 = all)
  *   "edit_wave_min" DG_EDIT_WAVE_MIN edited messages at least this long take the wave route of the splice (4096; 0 = all)
  *   "edit_lanes"  DG_EDIT_LANES   lanes per message on the splice's lane route: 1, 4 or 16 (4)
+ *   "kids_wide_min" DG_KIDS_WIDE_MIN a list, set or map node of fixed-size entries with at least this many children
+ *                                 is emitted one lane per record (256; 0 = never)
+ *   "kids_no_scan" (no env)       timing only: 1 = dg_kids_* calls leave the scan out, so d_rec_off is not written
+ *                                 (tools/kids_bench.py times the count pass alone with it, without d_recs)
  *   "edit_reuse_rec" (no env)     timing only: 1 = an edit launch of as many messages as the context's previous
  *                                 one skips the lookup and splices from its records (tools/edit_bench.py times the
  *                                 splice alone with it; another batch or path gives undefined results)
@@ -726,6 +731,61 @@ int dg_edit_batch_device(dg_ctx *ctx, const dg_edit *e, uint8_t root_type, const
 int dg_edit_batch_host(dg_ctx *ctx, const dg_edit *e, uint8_t root_type, const uint8_t *thrift, const uint64_t *in_off,
                        uint64_t n, uint8_t val_type, const uint8_t *val, const uint64_t *val_off, uint64_t val_len,
                        uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret, uint64_t *out_need);
+
+/* ------------------------------------------------------------------------
+ * kids: batched Children over Thrift-binary messages (the reference's
+ * thrift/generic Node.Children / PathNode.scanChildren, node.go:1133-1154,
+ * path.go:796-836, 1121-1248). For every message of a batch and the node at
+ * the end of ONE path (a dg_path of exactly one path; the empty path is the
+ * message's root) the table of the node's children, or with
+ * DG_KIDS_F_RECURSE the whole subtree below it in preorder: what
+ * v.GetByPath(path...) followed by .Children(&out, recurse, &Options{}) gives.
+ *
+ * The path is looked up as dg_tget_* does; a lookup that fails gives the
+ * message its status (DG_TGET_NOT_FOUND / E_READ / E_TYPE) and step. A node
+ * that is no struct, list, set or map is DG_KIDS_E_UNSUPPORTED
+ * (meta.ErrUnsupportedType). The node's header, and in recursive mode every
+ * nested container's, is read with ReadListBegin / ReadMapBegin (type bytes
+ * Valid(), sizes not negative: stricter than the skip, so a list<type 5> of
+ * size 0 is DG_TGET_E_READ here); every child's end comes from SkipType. Map
+ * keys: a STRING key is DG_PS_STRKEY, an I08 / I16 / I32 / I64 key
+ * DG_PS_INTKEY (ReadInt: an I08 key is unsigned), any other key type
+ * DG_PS_BINKEY over the bytes SkipType delimits; keys are never descended
+ * into. Any failure makes the message DG_TGET_E_READ with no records. Depth:
+ * 1023 levels including the node for a non-empty path, 1023 below each direct
+ * child for the empty path (the reference's outermost skip). Trailing bytes
+ * after the root are ignored. The Go's storage options (StoreChildrenById,
+ * StoreChildrenByHash, NotScanParentNode) have no counterpart: records come in
+ * wire order and a container's record carries its real end.
+ *
+ * Records (dgj2t_defs.h): dg_kids_head per message, dg_kid_rec per child,
+ * message i's at d_recs[d_rec_off[i], d_rec_off[i + 1]); d_rec_off[n] is the
+ * total. head.direct of a list, set or map is Node.Len(), so a call without
+ * d_recs is batched Len.
+ *
+ * Device buffers, stream-ordered, async (stream NULL: the context's). Messages
+ * and root_type as dg_tget_batch_device (the arena readable 16 bytes past its
+ * end; n below 2^32). d_head (n entries) and d_recs are 16-byte aligned,
+ * d_rec_off has n + 1 entries. Stages: count kernel -> scan -> emit kernel.
+ * d_recs NULL stops after the scan. DG_KIDS_F_COUNTED: d_head / d_rec_off were
+ * filled by an earlier call with the same batch, path and flags; the call
+ * emits only. A message whose records would pass rec_cap writes none and gets
+ * DG_KIDS_E_OVERFLOW (count 0); no record is stored at an index >= rec_cap and
+ * d_rec_off[n] still tells the need. A list, set or map node of fixed-size
+ * entries with at least "kids_wide_min" children is emitted one lane per
+ * record. n = 0 returns DG_OK and launches nothing. DG_E_ARG for a path set of
+ * more or fewer than one path. max_len: the batch's longest message or 0, a
+ * hint. */
+int dg_kids_batch_device(dg_ctx *ctx, const dg_path *path, uint8_t root_type, uint32_t flags, const uint8_t *d_thrift,
+                         const uint64_t *d_in_off, uint64_t n, dg_kids_head *d_head, uint64_t *d_rec_off,
+                         dg_kid_rec *d_recs, uint64_t rec_cap, void *stream, uint64_t max_len);
+/* Host buffers, synchronous (no spare bytes needed; DG_KIDS_F_COUNTED is
+ * refused). head and rec_off are always filled and *need = rec_off[n]. recs
+ * NULL with rec_cap 0 stops there (sizing, Len); otherwise DG_E_NOMEM when
+ * rec_cap < *need, and no message is ever DG_KIDS_E_OVERFLOW. */
+int dg_kids_batch_host(dg_ctx *ctx, const dg_path *path, uint8_t root_type, uint32_t flags, const uint8_t *thrift,
+                       const uint64_t *in_off, uint64_t n, dg_kids_head *head, uint64_t *rec_off, dg_kid_rec *recs,
+                       uint64_t rec_cap, uint64_t *need);
 
 /* Timing helper for benchmarks: launch the device batch `iters` times on the
  * context stream bracketed by HIP events; returns total milliseconds of GPU

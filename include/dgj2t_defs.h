@@ -254,6 +254,34 @@ typedef struct dg_cut_lit {
 #define DG_EDIT_E_OVERFLOW 0xF0u  /* slot too small (the value of DG_ST_OUT_OVERFLOW) */
 #define DG_EDIT_EXISTED (1ull << 8) /* the path was there: a replace or a delete, not an insert or a no-op */
 
+/* kids (batched Children, include/dgj2t.h dg_kids_*): the statuses a message
+ * can have besides DG_TGET_OK / NOT_FOUND / E_READ / E_TYPE, the flags, and the
+ * two records (little-endian, no padding) */
+#define DG_KIDS_E_UNSUPPORTED 4u   /* meta.ErrUnsupportedType: the node is no struct, list, set or map */
+#define DG_KIDS_E_OVERFLOW 0xF0u   /* the message's records would pass rec_cap (the value of DG_ST_OUT_OVERFLOW) */
+#define DG_KIDS_F_RECURSE 1u       /* Children(recurse = true): the whole subtree, preorder */
+#define DG_KIDS_F_COUNTED 2u       /* d_head / d_rec_off come from an earlier call: emit only */
+#define DG_KIDS_NO_PARENT 0xFFFFFFFFu
+typedef struct dg_kid_rec {
+    uint32_t start, end; /* the child's value in the message */
+    uint32_t key_start;  /* STRKEY: the key's bytes at key_start + 4; BINKEY: at key_start; a field: start - 3; an
+                            element: start */
+    uint32_t parent;     /* index, among this message's records, of the enclosing child; DG_KIDS_NO_PARENT for a
+                            direct child */
+    int64_t key;         /* field id, index or int key; STRKEY / BINKEY: the key's length */
+    uint8_t type, kind;  /* wire type; DG_PS_FIELD / INDEX / STRKEY / INTKEY / BINKEY */
+    uint16_t depth;      /* 1 = a direct child */
+    uint32_t n_desc;     /* records in the subtree below this one (0 in one-level mode and for scalars) */
+} dg_kid_rec; /* 32 bytes */
+typedef struct dg_kids_head {
+    uint32_t count;  /* records of the message, 0 unless DG_TGET_OK */
+    uint32_t direct; /* direct children (Node.Len of a list, set or map); not OK: the failing step, the path's
+                        length for a failure in the scan */
+    uint32_t start;  /* where the node starts (OK and DG_KIDS_E_UNSUPPORTED / E_OVERFLOW) */
+    uint8_t type, key_type, elem_type; /* the node's types; key and element types 0 for a struct */
+    uint8_t status;
+} dg_kids_head; /* 16 bytes */
+
 /* t2j (Thrift binary -> JSON, conv/t2j) option bits: the conv.Options fields
  * conv/t2j/impl.go reads (conv/api.go:52-121) */
 #define DG_T2J_BYTE_AS_UINT8 (1ull << 0)     /* ByteAsUint8 */
