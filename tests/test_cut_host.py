@@ -238,6 +238,43 @@ def test_walk_fuzz(walk):
         both(walk, msgs + bad, wide, narrow, o)
 
 
+def family_on_both_routes(walk, fam, opts_words=G.ALL_OPTS):
+    unset = parse(fam.blob())["U"]  # dg_cut_slot_bound: a message of one STOP can grow by every literal
+    caps = [len(m) * (1 + unset) + 64 for m in fam.msgs]
+    for o in opts_words:
+        for route in (1, 0):
+            got, _ = walk(fam.msgs, fam.blob(), o, route, caps=caps)
+            for i, (g, w) in enumerate(zip(got, fam.want(o))):
+                assert g == w, "%s, opts %d, route %d, message %d (%r...): got %x / %d bytes, checker %x / %d" % (
+                    fam.name, o, route, i, fam.msgs[i][:24], g[0], len(g[1]), w[0], len(w[1]))
+
+
+def test_wide_corpus_is_worth_running():
+    """what test_gpu_cut_shapes.py asserts of the wide structs' corpus, from the checker alone"""
+    G.check_wide_corpus(G.wide_cases())
+    G.check_wide_corpus(G.wide_cases(G.WIDE_GPU_NS))
+    for fam in [G.staged_family(d) for d in G.STAGED_DELTAS] + [G.padded_family()]:
+        fam.assert_worth_running()
+
+
+@pytest.mark.parametrize("mode", G.WIDE_MODES)
+def test_walk_wide_structs(walk, mode):
+    """1 to 300 fields, up to 64 of them tracked: bit 63 of the live mask required and as a literal, the field
+    search over more than 33 fields, ids at the int16 extremes"""
+    for n, m, top in G.wide_cases():
+        if m == mode:
+            family_on_both_routes(walk, G.wide_family(n, m, top))
+
+
+def test_walk_plans_around_the_lane_routes_lds_copy(walk):
+    cap = G.lane_plan_cap()
+    assert [G.tab_len(G.staged_family(d).blob()) - cap for d in G.STAGED_DELTAS] == [-8, 0, 8]
+    for d in G.STAGED_DELTAS:
+        family_on_both_routes(walk, G.staged_family(d))
+    assert G.tab_len(G.padded_family().blob()) > 3 * cap
+    family_on_both_routes(walk, G.padded_family())
+
+
 def test_walk_runs_and_alignments(walk):
     w, n = G.run_pair()
     msgs = G.run_messages()
@@ -304,6 +341,9 @@ def test_stand_alone_program_under_sanitizers(tmp_path):
             (msgs[:48] + bad[:48], wide, narrow, R.DISALLOW_UNKNOWN),
             ([G.chain_message("S" * (d - 1)) for d in (8, 9, 64, 65)], node, node_n, R.WRITE_DEFAULT),
             (G.run_messages()[::37], *G.run_pair(), 0)]
+    # 300 fields with sparse ids and 64 tracked; the fuzz shape with a plan of 16 KB
+    wide300, padded = G.wide_family(300, "sparse"), G.padded_family()
+    sets += [(wide300.msgs, wide300.frm, wide300.to, R.WRITE_DEFAULT), (padded.msgs, padded.frm, padded.to, R.WRITE_DEFAULT)]
     files, count, total, n_msgs = [], {}, 0, 0
     for k, (ms, frm, to, o) in enumerate(sets):
         want = G.expect(ms, frm, to, o)
