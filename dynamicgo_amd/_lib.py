@@ -25,6 +25,8 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_path_create", "dg_path_destroy", "dg_path_count", "dg_tget_batch_device", "dg_tget_batch_host",
            "dg_cut_create", "dg_cut_destroy", "dg_cut_slot_bound", "dg_cut_batch_device", "dg_cut_batch_host",
            "dg_edit_create", "dg_edit_destroy", "dg_edit_slot_bound", "dg_edit_batch_device", "dg_edit_batch_host",
+           "dg_editm_create", "dg_editm_destroy", "dg_editm_items", "dg_editm_slot_bound", "dg_editm_batch_device",
+           "dg_editm_batch_host",
            "dg_kids_batch_device", "dg_kids_batch_host"]
 
 _lib = None
@@ -121,6 +123,12 @@ def lib() -> C.CDLL:
         "dg_edit_slot_bound": (u64, [vp, u64, u64]),
         "dg_edit_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, u64]),
         "dg_edit_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, C.c_uint8, vp, vp, u64, vp, u64, vp, vp, P64]),
+        "dg_editm_create": (i32, [vp, C.c_char_p, sz, u32, C.POINTER(vp)]),
+        "dg_editm_destroy": (None, [vp]),
+        "dg_editm_items": (u32, [vp]),
+        "dg_editm_slot_bound": (u64, [vp, u64, u64]),
+        "dg_editm_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64]),
+        "dg_editm_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, P64]),
         "dg_kids_batch_device": (i32, [vp, vp, C.c_uint8, u32, vp, vp, u64, vp, vp, vp, u64, vp, u64]),
         "dg_kids_batch_host": (i32, [vp, vp, C.c_uint8, u32, vp, vp, u64, vp, vp, vp, u64, P64]),
     }

@@ -4,7 +4,7 @@
  * orders a shared buffer across streams, the context, descriptor and
  * per-stream scratch records, the entry guard, the argument records of one
  * batch and the error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host, edit_host, kids_host and j2t_pipe use them).
+ * tget_host, cut_host, edit_host, editm_host, kids_host and j2t_pipe use them).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -313,6 +313,11 @@ struct dg_ctx {
     StreamOrder edit;
     DevArr<dg_tget_rec> edit_rec;
     uint64_t edit_rec_n = 0; /* messages of the launch that filled edit_rec */
+    /* editm (editm_host.hip): the lookup's (K + 1) n records of one batch, a
+     * scratch of its own so that edit_rec keeps what the edit_reuse_rec knob
+     * promises */
+    StreamOrder editm;
+    DevArr<dg_tget_rec> editm_rec;
     /* kids (kids_host.hip): the deep pass's frames (32 MB, allocated by the
      * first call), the deep and wide queues (n entries each), the two
      * alternating counter sets {deep, wide} and the scan's tile sums */

@@ -1,4 +1,6 @@
-"""thrift/generic on the GPU. Batched Children (the fourth part of this
+"""thrift/generic on the GPU. Batched SetMany (EditManyPlan, set_many_batch,
+unset_many_batch, edit_many_device: several children of one node edited in one
+pass), batched Children (the fourth part of this
 module: children_batch, children_records, children_device), batched
 SetByPath / UnsetByPath (the third
 part of this module: EditPlan, set_by_path_batch, unset_by_path_batch,
@@ -515,8 +517,9 @@ def marshal_to_device(plan: CutPlan, thrift, in_off, n: int, out, out_off, out_l
 EDIT_SET, EDIT_UNSET = 1, 2  # DG_EDIT_SET / DG_EDIT_UNSET (include/dgj2t_defs.h)
 EDIT_OK, EDIT_NOT_FOUND, EDIT_E_READ, EDIT_E_TYPE, EDIT_E_OVERFLOW = 0, 1, 2, 3, 0xF0
 EDIT_EXISTED = 1 << 8
+EDITM_E_SAME = 5  # DG_EDITM_E_SAME: only a many-edit (EditManyPlan) returns it
 EDIT_ERROR_NAMES = {EDIT_OK: None, EDIT_NOT_FOUND: "ErrNotFound", EDIT_E_READ: "ErrRead",
-                    EDIT_E_TYPE: "ErrDismatchType", EDIT_E_OVERFLOW: "ErrOverflow"}
+                    EDIT_E_TYPE: "ErrDismatchType", EDITM_E_SAME: "ErrSame", EDIT_E_OVERFLOW: "ErrOverflow"}
 
 
 class EditPlan:
@@ -548,8 +551,8 @@ class EditPlan:
          reference silently does nothing);
       7. the empty path (`*self = sub`) is refused: ValueError here, DG_E_ARG in
          the C ABI.
-    SetMany and several paths in one plan are out of scope: apply a second
-    edit to the first one's output."""
+    Several children of one node in one pass: EditManyPlan (SetMany). Items
+    under different parents stay a second edit on the first one's output."""
 
     def __init__(self, path, op: int, desc=None, ctx: Optional[Context] = None):
         self.op = int(op)
@@ -693,6 +696,198 @@ def edit_device(plan: EditPlan, thrift, in_off, n: int, val_type: int, val, val_
     _lib.check(_lib.lib().dg_edit_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n, val_type,
                                                _ptr(val), _ptr(val_off), val_len, _ptr(out), _ptr(out_off),
                                                _ptr(out_len), _ptr(ret), s, max_len))
+
+
+# ---------------------------------------------------------------------------
+# SetMany: several children of one node rewritten in one pass over every
+# message of a batch (thrift/generic/node.go:930-1007; dg_editm_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+EDITM_MAX_ITEMS = MAX_PATHS - 1  # DG_EDITM_MAX_ITEMS
+
+
+def _step_class(kind: int) -> int:
+    return 0 if kind == PS_FIELD else 1 if kind == PS_INDEX else 2
+
+
+class EditManyPlan:
+    """One many-edit on one context's device (dg_editm): a `parent` path of 0
+    to 15 steps, 1 to 7 last `steps` below it and an op. Every step is one
+    Path; all are of one class: all fields (PathFieldId / PathFieldName,
+    resolved through `desc` by compile_paths), all indexes, or all keys
+    (PathStrKey, PathIntKey and PathBinKey may mix).
+
+    EDIT_SET: every item is decided as EditPlan decides a single SET. Found
+    items are replaced in place; missing ones are all inserted at the front
+    of the container in the order given, and the count is patched once.
+    EDIT_UNSET: every item is decided as a single UNSET on the ORIGINAL
+    message (indexes do not shift between items). A message is edited as a
+    whole or not at all: the first failing item in item order gives the
+    message its status.
+
+    Where this differs from the reference, besides EditPlan's 1 to 7:
+      8. a replace checks the wire type (replaceMany does not);
+      9. items that resolve to overlapping spans (a string key and the same
+         key as a binary key, an existing index twice) are ErrSame (the
+         reference writes a corrupt buffer); two MISSING duplicates are a
+         legal double insert;
+      10. mixed step classes are refused: ValueError here, DG_E_ARG in the C
+          ABI."""
+
+    def __init__(self, parent, steps, op: int, desc=None, ctx: Optional[Context] = None):
+        self.op = int(op)
+        steps = list(steps)
+        if not 1 <= len(steps) <= EDITM_MAX_ITEMS:
+            raise ValueError("%d items (1 to %d)" % (len(steps), EDITM_MAX_ITEMS))
+        paths = [_resolve(list(parent) + [st], desc) for st in steps]
+        if len({_step_class(p[-1].kind) for p in paths}) != 1:
+            raise ValueError("mixed step classes")
+        self.k = len(steps)
+        self.blob = compile_paths(paths)
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dg_editm_create(self.ctx.h, self.blob, len(self.blob), self.op, C.byref(h)))
+        self.h = h
+
+    def slot_bound(self, length: int, val_total: int = 0) -> int:
+        """The exact worst case of one message's output (dg_editm_slot_bound);
+        val_total: the K values' lengths together."""
+        return int(_lib.lib().dg_editm_slot_bound(self.h, length, val_total))
+
+    def close(self):
+        if self.h:
+            _lib.lib().dg_editm_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class EditManyResult:
+    """One message: .status (EDIT_OK, EDIT_NOT_FOUND, EDIT_E_READ, EDIT_E_TYPE,
+    EDITM_E_SAME), .existed (a tuple of K bools: item j was a replace or a
+    drop; all False unless EDIT_OK), .item (the failing item, 0 when OK),
+    .aux, .raw (the edited message, empty unless EDIT_OK), .error (None,
+    "ErrNotFound", "ErrRead", "ErrDismatchType", "ErrSame")."""
+    __slots__ = ("status", "existed", "item", "raw", "error", "aux")
+
+    def __init__(self, ret: int, raw: bytes, k: int):
+        ret = int(ret)
+        self.status, self.aux = ret & 0xFF, ret >> 32
+        self.existed = tuple(bool(ret >> (8 + j) & 1) for j in range(k))
+        self.item = ret >> 16 & 7
+        self.raw = raw if self.status == EDIT_OK else b""
+        self.error = EDIT_ERROR_NAMES.get(self.status, "ErrRead")
+
+    def __repr__(self):
+        return "EditManyResult(status=%d, existed=%s, item=%d, aux=%d, %d bytes)" % (
+            self.status, self.existed, self.item, self.aux, len(self.raw))
+
+
+def _editm_batch(msgs, plan: EditManyPlan, values, val_types, root_type: int) -> List[EditManyResult]:
+    n, k = len(msgs), plan.k
+    L = _lib.lib()
+    vt = np.asarray(val_types if val_types is not None else [0] * k, dtype=np.uint8)
+    vl = np.zeros(k, dtype=np.uint64)
+    if n == 0:
+        _lib.check(L.dg_editm_batch_host(plan.ctx.h, plan.h, root_type, None, None, 0, vt.ctypes.data, None, None,
+                                         vl.ctypes.data, None, 0, None, None, None))
+        return []
+    lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
+    in_off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(lens, out=in_off[1:])
+    arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+    val = val_off = None
+    vtotal = 0
+    if values is not None:
+        if all(isinstance(v, (bytes, bytearray)) for v in values):
+            vl[:] = [len(v) for v in values]
+            val = np.frombuffer(b"".join(bytes(v) for v in values) + b"\0" * 16, dtype=np.uint8)
+        else:
+            for v in values:
+                if not isinstance(v, (bytes, bytearray)) and len(v) != n:
+                    raise ValueError("%d values for %d messages" % (len(v), n))
+            flat = [bytes(v) if isinstance(v, (bytes, bytearray)) else bytes(v[i]) for i in range(n) for v in values]
+            val_off = np.zeros(n * k + 1, dtype=np.uint64)
+            np.cumsum(np.fromiter((len(v) for v in flat), dtype=np.uint64, count=n * k), out=val_off[1:])
+            val = np.frombuffer(b"".join(flat) + b"\0" * 16, dtype=np.uint8)
+            vtotal = int(val_off[n * k])
+    out_off = np.zeros(n + 1, dtype=np.uint64)
+    ret = np.zeros(n, dtype=np.uint64)
+    need = C.c_uint64(0)
+    cap = int(in_off[n]) + vtotal  # a guess; the call says what it needs
+    while True:
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        rc = L.dg_editm_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
+                                   vt.ctypes.data, None if val is None else val.ctypes.data,
+                                   None if val_off is None else val_off.ctypes.data, vl.ctypes.data, out.ctypes.data,
+                                   cap, out_off.ctypes.data, ret.ctypes.data, C.byref(need))
+        if rc == -3 and need.value > cap:  # DG_E_NOMEM: the inserts outgrew the guess
+            cap = int(need.value)
+            continue
+        _lib.check(rc)
+        break
+    return [EditManyResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes(), k) for i in range(n)]
+
+
+def set_many_batch(msgs: Sequence[bytes], parent, items, desc=None, root_type: int = STRUCT,
+                   ctx: Optional[Context] = None) -> List[EditManyResult]:
+    """SetMany for every message of a batch (dg_editm_batch_host): below the
+    node at `parent` (a list of Path steps, possibly empty), every item
+    (step, value_or_values, val_type) sets the child at `step` to the value's
+    Thrift-binary bytes, taken as given, of wire type val_type: one `bytes`
+    for all messages or a sequence with one entry per message. `parent` may
+    be an EditManyPlan of op EDIT_SET; its steps are then the plan's and the
+    items' steps are not looked at. Semantics: EditManyPlan."""
+    plan = parent if isinstance(parent, EditManyPlan) else \
+        EditManyPlan(parent, [it[0] for it in items], EDIT_SET, desc, ctx)
+    try:
+        if plan.op != EDIT_SET or plan.k != len(items):
+            raise ValueError("set_many_batch needs an EDIT_SET plan of as many steps as items")
+        return _editm_batch(msgs, plan, [it[1] for it in items], [it[2] for it in items], root_type)
+    finally:
+        if plan is not parent:
+            plan.close()
+
+
+def unset_many_batch(msgs: Sequence[bytes], parent, steps=None, desc=None, root_type: int = STRUCT,
+                     ctx: Optional[Context] = None) -> List[EditManyResult]:
+    """The UNSET counterpart: the children at `steps` below `parent` (or an
+    EditManyPlan of op EDIT_UNSET) are dropped from every message, every step
+    addressing the original message. Semantics: EditManyPlan."""
+    plan = parent if isinstance(parent, EditManyPlan) else EditManyPlan(parent, steps, EDIT_UNSET, desc, ctx)
+    try:
+        if plan.op != EDIT_UNSET:
+            raise ValueError("unset_many_batch needs an EDIT_UNSET plan")
+        return _editm_batch(msgs, plan, None, None, root_type)
+    finally:
+        if plan is not parent:
+            plan.close()
+
+
+def edit_many_device(plan: EditManyPlan, thrift, in_off, n: int, val_types, val, val_off, val_lens, out, out_off,
+                     out_len, ret, root_type: int = STRUCT, stream=None, max_len: int = 0):
+    """Device-resident batch (dg_editm_batch_device) over torch tensors or raw
+    device pointers, as edit_device. val_types and val_lens are HOST
+    sequences of K entries; val uint8 with 16 spare bytes; val_off
+    int64[n * K + 1], message-major (item j of message i is val[val_off[i*K+j],
+    val_off[i*K+j+1]); val_lens[j] is then item j's longest value or 0), or
+    None: val holds the K values back to back, val_lens[j] bytes each, for
+    every message. ret int64[n]: status | existed mask << 8 | failing item
+    << 16 | aux << 32. An UNSET plan ignores the value arguments."""
+    if stream is None and hasattr(thrift, "device"):
+        import torch
+        stream = torch.cuda.current_stream(thrift.device)
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    vt = np.asarray(val_types if val_types is not None else [0] * plan.k, dtype=np.uint8)
+    vl = np.asarray(val_lens if val_lens is not None else [0] * plan.k, dtype=np.uint64)
+    if len(vt) != plan.k or len(vl) != plan.k:
+        raise ValueError("val_types / val_lens need %d entries" % plan.k)
+    _lib.check(_lib.lib().dg_editm_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n,
+                                                vt.ctypes.data, _ptr(val), _ptr(val_off), vl.ctypes.data, _ptr(out),
+                                                _ptr(out_off), _ptr(out_len), _ptr(ret), s, max_len))
 
 
 # ---------------------------------------------------------------------------

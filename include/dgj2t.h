@@ -85,13 +85,15 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *   "cut_wave_min" DG_CUT_WAVE_MIN messages at least this long take the wave route of the cut (4096; 0 = all)
  *   "edit_wave_min" DG_EDIT_WAVE_MIN edited messages at least this long take the wave route of the splice (4096; 0 = all)
  *   "edit_lanes"  DG_EDIT_LANES   lanes per message on the splice's lane route: 1, 4 or 16 (4)
+ *                                 (both knobs route dg_edit_* and dg_editm_* alike)
  *   "kids_wide_min" DG_KIDS_WIDE_MIN a list, set or map node of fixed-size entries with at least this many children
  *                                 is emitted one lane per record (256; 0 = never)
  *   "kids_no_scan" (no env)       timing only: 1 = dg_kids_* calls leave the scan out, so d_rec_off is not written
  *                                 (tools/kids_bench.py times the count pass alone with it, without d_recs)
  *   "edit_reuse_rec" (no env)     timing only: 1 = an edit launch of as many messages as the context's previous
  *                                 one skips the lookup and splices from its records (tools/edit_bench.py times the
- *                                 splice alone with it; another batch or path gives undefined results)
+ *                                 splice alone with it; another batch or path gives undefined results;
+ *                                 dg_editm_* keeps records of its own and does not look at it)
  * Unknown names return DG_E_INVALID. Thread-safe (the context lock). */
 int dg_ctx_set_knob(dg_ctx *ctx, const char *name, int64_t value);
 int dg_ctx_get_knob(dg_ctx *ctx, const char *name, int64_t *value);
@@ -687,8 +689,8 @@ int dg_cut_batch_host(dg_ctx *ctx, const dg_cut *plan, uint64_t opts, const uint
  *      it is DG_EDIT_E_TYPE.
  *   7. The empty path (`*self = sub`) is no edit of a message: dg_edit_create
  *      refuses it with DG_E_ARG.
- * SetMany, or several paths in one edit, are out of scope: a second edit is a
- * second call on the first one's output.
+ * Several children of one node in one edit: dg_editm_* below (SetMany). Items
+ * under different parents stay a second call on the first one's output.
  *
  * dg_edit_create takes the DG_PATH_MAGIC blob of dg_path_create with exactly
  * one path of at least one step (DG_E_ARG otherwise, and for every blob
@@ -731,6 +733,78 @@ int dg_edit_batch_device(dg_ctx *ctx, const dg_edit *e, uint8_t root_type, const
 int dg_edit_batch_host(dg_ctx *ctx, const dg_edit *e, uint8_t root_type, const uint8_t *thrift, const uint64_t *in_off,
                        uint64_t n, uint8_t val_type, const uint8_t *val, const uint64_t *val_off, uint64_t val_len,
                        uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret, uint64_t *out_need);
+
+/*
+ * editm: batched SetMany (the reference's Node.SetMany with getMany,
+ * setNotFound per missing item and replaceMany, thrift/generic/node.go:930-1007)
+ * and its UNSET counterpart. One many-edit is a parent path of 0 to
+ * DG_TGET_MAX_STEPS - 1 steps, K items (1 <= K <= DG_EDITM_MAX_ITEMS), each ONE
+ * last step below the parent, and one op, applied to every message of a batch:
+ * what v.GetByPath(parent...).SetMany(items) gives, written back into the whole
+ * message. The K last steps are of one class: all FIELD, all INDEX, or all key
+ * steps (STRKEY, INTKEY and BINKEY may mix). Parent and the K full paths are one
+ * path set, so one lookup launch serves all items; then one splice writes the
+ * message once with all K cuts.
+ *
+ * DG_EDIT_SET: item j carries a value of wire type val_types[j] and is decided
+ * exactly as dg_edit decides a single SET (statuses and deviations 1-7 above).
+ * Found items are replaced in place; missing items are all inserted at the front
+ * of the container in the order the items were given (the reference's
+ * TestSetMany reads two Index(1024) inserts back at indexes 0 and 1); the count
+ * is patched once, to int32(count + inserts), wrapping.
+ * DG_EDIT_UNSET: each item is decided as a single UNSET; all items address the
+ * ORIGINAL message (indexes do not shift between items); the count becomes
+ * int32(count - dropped); a missed parent leaves the message unchanged, DG_EDIT_OK.
+ * A message is edited as a whole or not at all: if an item's decision fails the
+ * message fails with that item's status and aux (the first failing item in item
+ * order) and nothing is written. Two items that resolve to overlapping spans
+ * (STRKEY "a" and BINKEY "a" on one entry, an existing index given twice) are
+ * DG_EDITM_E_SAME; the item reported is the second of the first overlapping pair
+ * in message order (equal spans in item order). Two MISSING duplicates are a
+ * legal double insert.
+ * d_ret[i] = status | existed mask << 8 | failing item << 16 | aux << 32 (bit
+ * 8 + j set when item j was a replace or a drop; the item field is 0 when OK); for
+ * K = 1 the word is dg_edit's. d_out_len[i] as dg_edit's.
+ *
+ * Deviations from the reference besides 1-7:
+ *   8. A replace checks the wire type (replaceMany does not).
+ *   9. Overlapping items are DG_EDITM_E_SAME (replaceMany writes a corrupt buffer).
+ *  10. Mixed step classes are refused by dg_editm_create with DG_E_ARG.
+ *
+ * dg_editm_create takes a DG_PATH_MAGIC blob of 1 to DG_EDITM_MAX_ITEMS paths of
+ * equal length >= 1 that are identical in every step but the last: path j is
+ * parent + item j's step. The blob is judged before the context is looked at
+ * (DG_E_ARG with dg_path_create's texts, "N items", "paths of unequal length",
+ * "paths differ before their last step", "mixed step classes"). Duplicate last
+ * steps are not refused.
+ */
+typedef struct dg_editm dg_editm;
+int dg_editm_create(dg_ctx *ctx, const void *path_blob, size_t len, uint32_t op, dg_editm **out);
+void dg_editm_destroy(dg_editm *e);
+uint32_t dg_editm_items(const dg_editm *e);
+/* The exact worst case of one message's output: DG_EDIT_UNSET: len;
+ * DG_EDIT_SET: len + val_total (the K values' lengths together) + the sum over
+ * the items of what each last step can add (as dg_edit_slot_bound). */
+uint64_t dg_editm_slot_bound(const dg_editm *e, uint64_t len, uint64_t val_total);
+/* As dg_edit_batch_device (the arenas' spare bytes, the slot rules, max_len and
+ * the routes "edit_lanes" / "edit_wave_min"); n * (K + 1) below 2^32. val_types
+ * and val_lens are HOST arrays of K entries. With d_val_off (n * K + 1 entries,
+ * message-major) item j of message i is d_val[d_val_off[i*K+j], d_val_off[i*K+j+1])
+ * and val_lens[j] is the longest value of item j, a hint (0 = unknown); with
+ * d_val_off NULL d_val holds the K values back to back (val_lens[j] bytes each)
+ * and every message gets them. The lookup's (K + 1) n records live in a scratch
+ * of the context of their own, ordered across streams. */
+int dg_editm_batch_device(dg_ctx *ctx, const dg_editm *e, uint8_t root_type, const uint8_t *d_thrift,
+                          const uint64_t *d_in_off, uint64_t n, const uint8_t *val_types, const uint8_t *d_val,
+                          const uint64_t *d_val_off, const uint64_t *val_lens, uint8_t *d_out,
+                          const uint64_t *d_out_off, uint32_t *d_out_len, uint64_t *d_ret, void *stream,
+                          uint64_t max_len);
+/* Host buffers, synchronous, as dg_edit_batch_host: val_off has n * K + 1 entries
+ * or is NULL (then val holds the K values back to back, val_lens[j] bytes each). */
+int dg_editm_batch_host(dg_ctx *ctx, const dg_editm *e, uint8_t root_type, const uint8_t *thrift,
+                        const uint64_t *in_off, uint64_t n, const uint8_t *val_types, const uint8_t *val,
+                        const uint64_t *val_off, const uint64_t *val_lens, uint8_t *out, uint64_t out_cap,
+                        uint64_t *out_off, uint64_t *ret, uint64_t *out_need);
 
 /* ------------------------------------------------------------------------
  * kids: batched Children over Thrift-binary messages (the reference's

@@ -254,6 +254,13 @@ typedef struct dg_cut_lit {
 #define DG_EDIT_E_OVERFLOW 0xF0u  /* slot too small (the value of DG_ST_OUT_OVERFLOW) */
 #define DG_EDIT_EXISTED (1ull << 8) /* the path was there: a replace or a delete, not an insert or a no-op */
 
+/* editm (batched SetMany, include/dgj2t.h dg_editm_*): up to DG_EDITM_MAX_ITEMS
+ * last steps below one parent path in one edit, so that parent + items are one
+ * path set. The return word is status | existed mask << 8 (bit 8 + j: item j was
+ * a replace or a drop) | failing item << 16 (3 bits, 0 when OK) | aux << 32 */
+#define DG_EDITM_MAX_ITEMS (DG_TGET_MAX_PATHS - 1u)
+#define DG_EDITM_E_SAME 5u /* two items resolve to overlapping spans of the message (4 is DG_KIDS_E_UNSUPPORTED) */
+
 /* kids (batched Children, include/dgj2t.h dg_kids_*): the statuses a message
  * can have besides DG_TGET_OK / NOT_FOUND / E_READ / E_TYPE, the flags, and the
  * two records (little-endian, no padding) */
