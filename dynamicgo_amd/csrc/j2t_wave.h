@@ -181,6 +181,16 @@ DGI uint32_t wave_incl_sum(uint32_t v, uint32_t lane)
     }
     return v;
 }
+/* the same over 64-bit values: 64 lengths of up to 2^32 - 1 bytes each pass 32 bits */
+DGI uint64_t wave_incl_sum64(uint64_t v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        uint64_t u = __shfl_up(v, d);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
 template <class T>
 DGI T uni(T v) /* wave-uniform value -> SGPR */
 {
@@ -1582,8 +1592,8 @@ __global__ __launch_bounds__(256) void dg_pack_scan_kernel(const uint8_t *out, c
     for (uint64_t t0 = lo; t0 < hi; t0 += 256) {
         const uint64_t i = t0 + tid;
         const uint32_t len = i < hi ? msg_len(i) : 0u;
-        /* block exclusive scan of len */
-        uint32_t incl = wave_incl_sum(len, lane);
+        /* block exclusive scan of len, in 64 bits: the lengths a wave holds may pass 2^32 together */
+        const uint64_t incl = wave_incl_sum64(len, lane);
         if (lane == 63) red[w] = incl;
         __syncthreads();
         uint64_t wpre = 0;
