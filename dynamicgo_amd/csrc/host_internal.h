@@ -384,6 +384,7 @@ struct Entry {
 struct dg_desc {
     dg_ctx *ctx = nullptr;
     DevArr<uint8_t> d_blob;
+    DevArr<uint8_t> d_flat;     /* the flat kernel's image (flat_image.h); none when the blob cannot take that kernel */
     size_t len = 0;
     dg_desc_hdr hdr;
     DevArr<uint8_t> d_side;     /* t2j side table (dg_desc_attach_t2j) */

@@ -39,6 +39,7 @@
  * kernel's list as in the small kernel.
  */
 #pragma once
+#include "flat_image.h"
 #include "j2t_small.h"
 
 namespace dg {
@@ -72,6 +73,9 @@ constexpr uint32_t FL_CHUNK = DG_FL_CHUNK;       /* input bytes per chunk task (
 constexpr uint32_t FL_MAXTASK = 320;             /* chunk tasks per block (more: the message declines; C2 ~160) */
 constexpr uint32_t FL_KEYS = 32;                  /* name-table slots of the flat struct kept as a key table (larger: name table) */
 constexpr uint32_t FL_NESC = 8;                  /* escapes per message (more: the message declines; C1's string has 8) */
+static_assert(FLI_WLO == EL_WLO && FLI_WN == EL_WN, "the image's window is FastTabs' window");
+constexpr uint32_t FL_FMAPW = FL_SLOTS * FL_MPB / 8; /* 8-byte words of the field map (a byte per slot and message) */
+static_assert(FL_MAXTASK >= FL_FMAPW + FL_MPB, "the task area holds the field map and, behind it, an unstaged block's offsets");
 #ifndef DG_FL_WPE
 #define DG_FL_WPE 4 /* waves per SIMD the register budget is cut for: 128 VGPRs; LDS allows 4 blocks (16 waves) per CU */
 #endif
@@ -620,7 +624,7 @@ DGI uint32_t flat_write(S &src, const FField &F, const FastTabs &tb, O &o, lds_e
 }
 
 struct FlatParams {
-    const uint8_t *blob;
+    const uint8_t *img; /* the descriptor's image (flat_image.h): fli_len(hdr.total_len) bytes */
     dg_desc_hdr hdr;
     uint32_t *bail_count;
     uint32_t *bail_list;
@@ -710,10 +714,10 @@ struct FlatLds {
     uint64_t *a_ret;
     uint32_t *a_out_len, *a_bail_count, *a_bail_list;
     uint32_t a_nb, a_wrap; /* messages in the block; S.wrap */
-    uint64_t p10u[20];
-    double p10d[23];
-    uint64_t pw[EL_WN];                     /* Eisel-Lemire powers window (j2t_fast.h) */
 };
+/* the dynamic region (the descriptor's image) lies behind this one: a base
+ * off 16 bytes would turn its 16-byte LDS stores into replays */
+static_assert(sizeof(FlatLds) % 16 == 0, "the image behind FlatLds starts 16-byte aligned");
 
 template <int V>
 __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(DG_FL_WPE))) void j2t_flat_kernel(
@@ -726,43 +730,48 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(D
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint64_t b0 = (uint64_t)blockIdx.x * FL_MPB;
     const uint64_t b1 = b0 + FL_MPB < P.n ? b0 + FL_MPB : P.n;
+    const uint32_t nb = (uint32_t)(b1 - b0); /* >= 1: the grid is ceil(n / FL_MPB) */
+    constexpr uint32_t NT = 64 * FL_WAVES;
+    static_assert(FL_WAVES >= 4, "the prologue gives waves 0..3 a part each");
 
-    /* ---- 0. the block's JSON span to LDS (16-byte coalesced), the descriptor,
-     *      per-message offsets ---- */
-    const uint64_t lo = P.in_off[b0], hi = P.in_off[b1];
+    /* ---- 0. the block's JSON span (16-byte coalesced), the descriptor's
+     *      image and the per-message offsets to LDS: two dependent round trips
+     *      to memory, the span's bounds (scalar loads) and then the span.
+     *      Everything else is issued beside them, and no vector load is waited
+     *      for before the JSON loads are out. All indices are clamped, never
+     *      branched on, so no load is sunk behind another load's wait. ---- */
+    /* (a) what needs the kernel arguments only: the image (flat_image.h: the
+     *     blob, then p10u, p10d and the Eisel-Lemire window, as they lie in
+     *     LDS), two 16-byte loads per thread (8 KiB; a longer image takes the
+     *     loop below); a lane's offset, in_off in the even waves and out_off
+     *     in the odd ones (entry b0 + nb is the block's last, always there);
+     *     and the three block-uniform entries */
+    const uint32_t blob16 = fli_blob16(S.hdr.total_len);
+    const uint32_t ni = (blob16 + FLI_TABS) >> 4;
+    const uint4 *gi = (const uint4 *)S.img;
+    const uint4 i0 = gi[min(tid, ni - 1)], i1 = gi[min(tid + NT, ni - 1)];
+    const uint64_t *po = (wave & 1) ? P.out_off : P.in_off;
+    const uint64_t ov = po[b0 + min(lane, nb)];
+    const uint64_t lo = P.in_off[b0], hi = P.in_off[b1], oend = P.out_off[b1];
+    /* (b) the span, as soon as its bounds are there */
     const uint64_t base = lo & ~15ull;
     const bool staged = hi - base <= (uint64_t)FL_STAGEW * 8;
-    if (staged) {
-        /* every thread's (up to 4) 16-byte loads issued before any is
-         * stored: one HBM round trip for the block's span, not one per
-         * loop trip */
-        const uint4 *gs = (const uint4 *)(P.json + base); /* arena: 16 readable bytes past the end */
-        uint4 *ls = (uint4 *)L.in;
-        const uint32_t nw = (uint32_t)((hi - base + 15) >> 4);
-        constexpr uint32_t NT = 64 * FL_WAVES;
-        static_assert(FL_STAGEW * 8 / 16 <= 4 * NT, "four 16-byte loads per thread cover the stage");
-        if (nw) { /* unconditional loads (clamped index), conditional stores: no branch between the loads */
-            const uint32_t l = nw - 1;
-            const uint4 v0 = gs[min(tid, l)], v1 = gs[min(tid + NT, l)], v2 = gs[min(tid + 2 * NT, l)],
-                        v3 = gs[min(tid + 3 * NT, l)];
-            if (tid < nw) ls[tid] = v0;
-            if (tid + NT < nw) ls[tid + NT] = v1;
-            if (tid + 2 * NT < nw) ls[tid + 2 * NT] = v2;
-            if (tid + 3 * NT < nw) ls[tid + 3 * NT] = v3;
-        }
-    }
-    {
-        const uint4 *gd = (const uint4 *)S.blob;
-        uint4 *ld = (uint4 *)s_fdesc;
-        for (uint32_t k = tid; k < (S.hdr.total_len + 15) / 16; k += 64 * FL_WAVES) ld[k] = gd[k];
-    }
-    if (tid < 20) {
-        uint64_t v = 1;
-        for (uint32_t k = 0; k < tid; k++) v *= 10;
-        L.p10u[tid] = v;
-    }
-    if (tid < 23) L.p10d[tid] = P10[tid];
-    el_window_fill(L.pw, tid);
+    const uint32_t nw = staged ? (uint32_t)((hi - base + 15) >> 4) : 0u;
+    static_assert(FL_STAGEW * 8 / 16 <= 4 * NT, "four 16-byte loads per thread cover the stage");
+    /* every thread's 4 loads issued before any is stored: one HBM round trip
+     * for the span. No branch around them: a block with nothing to stage
+     * (nw = 0) reads the 16 bytes at base, which the arena always has (16
+     * readable bytes past its end), and stores nothing. */
+    const uint4 *gs = (const uint4 *)(P.json + base);
+    const uint32_t l = nw ? nw - 1 : 0u;
+    const uint4 v0 = gs[min(tid, l)], v1 = gs[min(tid + NT, l)], v2 = gs[min(tid + 2 * NT, l)],
+                v3 = gs[min(tid + 3 * NT, l)];
+    /* (c) the first wait: the offsets. Message `lane`'s pair is its own entry
+     *     and the next lane's (lane 63: the block-uniform last entry). Wave 0
+     *     keeps the input side, wave 1 the output side, wave 2 clears the
+     *     per-message words, wave 3 the field map. */
+    const uint64_t onx = __shfl_down(ov, 1);
+    const uint64_t nx = lane == 63 ? ((wave & 1) ? oend : hi) : onx;
     if (tid == 0) {
         L.rounds = 0;
         L.ntask = 0;
@@ -773,47 +782,55 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(D
         L.a_out_len = P.out_len;
         L.a_bail_count = S.bail_count;
         L.a_bail_list = S.bail_list;
-        L.a_nb = (uint32_t)(b1 - b0);
+        L.a_nb = nb;
         L.a_wrap = S.wrap;
     }
-    if (tid < FL_MPB) {
-        uint32_t ok = 0, n = 0, lw = 0, big = 0, cap = 0;
-        uint64_t oa = 0;
-        const uint64_t i = b0 + tid;
-        if (i < b1) {
-            const uint64_t a = P.in_off[i], b = P.in_off[i + 1];
-            const uint64_t n64 = b - a;
-            oa = P.out_off[i];
-            cap = (uint32_t)min(P.out_off[i + 1] - oa, (uint64_t)0xFFFFFFFFu);
-            const bool tobig = P.big_list && (n64 > P.big_max || n64 > FL_MAXLEN);
-            list_big_w(P, tobig, i, n64); /* the wave kernel */
-            if (tobig) {
-                big = 1;
-            } else if (n64 > 0 && n64 <= FL_MAXLEN) {
-                n = (uint32_t)n64;
-                if (staged) {
-                    ok = 1;
-                    lw = (uint32_t)(((a - base) >> 3) << 3) | (uint32_t)(a & 7);
-                } else {
-                    ok = 1; /* its own 256-byte slot, realigned to byte 0 */
-                    lw = (tid * FL_SLOTW) << 3;
-                }
-            }
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave); /* scalar: whole waves branch */
+    if (wv == 0) {
+        uint32_t ok = 0, n = 0, lw = 0, big = 0;
+        const bool live = lane < nb;
+        const uint64_t a = ov, n64 = live ? nx - a : 0;
+        const bool tobig = live && P.big_list && (n64 > P.big_max || n64 > FL_MAXLEN);
+        list_big_w(P, tobig, b0 + lane, n64); /* the wave kernel */
+        if (tobig) {
+            big = 1;
+        } else if (n64 > 0 && n64 <= FL_MAXLEN) {
+            n = (uint32_t)n64;
+            ok = 1;
+            if (staged) lw = (uint32_t)(((a - base) >> 3) << 3) | (uint32_t)(a & 7);
+            else lw = (lane * FL_SLOTW) << 3; /* its own 256-byte slot, realigned to byte 0 */
         }
-        L.ok[tid] = ok;
-        L.n[tid] = n;
-        L.lw[tid] = lw;
-        L.big[tid] = big;
-        L.oa[tid] = oa;
-        L.cap[tid] = cap;
-        L.plo[tid] = 0;
-        L.phi[tid] = 0;
-        L.oc[tid] = 0;
-        L.nfq[tid] = 0;
-        L.nesc[tid] = 0;
-        L.fseen[tid] = 0;
+        L.ok[lane] = ok;
+        L.n[lane] = n;
+        L.lw[lane] = lw;
+        L.big[lane] = big;
+        if (!staged) L.task[FL_FMAPW + lane] = a; /* for the copy below (the task area is free until the tasks) */
+    } else if (wv == 1) {
+        const bool live = lane < nb;
+        L.oa[lane] = live ? ov : 0;
+        L.cap[lane] = live ? (uint32_t)min(nx - ov, (uint64_t)0xFFFFFFFFu) : 0u;
+    } else if (wv == 2) {
+        L.plo[lane] = 0;
+        L.phi[lane] = 0;
+        L.oc[lane] = 0;
+        L.nfq[lane] = 0;
+        L.nesc[lane] = 0;
+        L.fseen[lane] = 0;
+    } else if (wv == 3) {
+        for (uint32_t k = lane; k < FL_FMAPW; k += 64) L.task[k] = ~0ull; /* the field map (in the task area): none */
     }
-    if (tid < FL_SLOTS * FL_MPB / 4) ((uint32_t *)(void *)L.task)[tid] = 0xFFFFFFFFu; /* the field map (in the task area): none */
+    /* (d) the second wait: the span and the image, stored as they came */
+    {
+        uint4 *ls = (uint4 *)L.in;
+        if (tid < nw) ls[tid] = v0;
+        if (tid + NT < nw) ls[tid + NT] = v1;
+        if (tid + 2 * NT < nw) ls[tid + 2 * NT] = v2;
+        if (tid + 3 * NT < nw) ls[tid + 3 * NT] = v3;
+        uint4 *li = (uint4 *)s_fdesc;
+        if (tid < ni) li[tid] = i0;
+        if (tid + NT < ni) li[tid + NT] = i1;
+        for (uint32_t k = tid + 2 * NT; k < ni; k += NT) li[k] = gi[k]; /* a blob over ~7 KiB */
+    }
     __syncthreads();
     const uint32_t g = tid & 3, m1 = tid >> 2; /* phase 1: 4 lanes per message */
     if (!staged) {
@@ -822,7 +839,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(D
          * shifted to start at byte 0 (two aligned global words per word; the
          * arena has 16 readable bytes past its end) */
         if (tid < FL_G * FL_MPB && L.ok[m1]) {
-            const uint64_t a = P.in_off[b0 + m1];
+            const uint64_t a = L.task[FL_FMAPW + m1]; /* in_off[b0 + m1], as wave 0 loaded it */
             const uint32_t nw = (L.n[m1] + 7) >> 3, sh = (uint32_t)(a & 7) << 3;
             const glb_u64 *gsrc = (const glb_u64 *)(const void *)P.json + (a >> 3);
             /* lane g: words g, g + 4, ... (<= 8 of them, 256 bytes); all its
@@ -849,8 +866,11 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(D
     return; /* ablation: launch, staging and the block's tables only */
 #endif
     const auto D = desc_view<3>((const __attribute__((address_space(3))) uint8_t *)(void *)s_fdesc, S.hdr);
-    const FastTabs tb{(const __attribute__((address_space(3))) uint64_t *)(void *)L.p10u, (lds_f64 *)(void *)L.p10d,
-                      (const __attribute__((address_space(3))) uint64_t *)(void *)L.pw};
+    /* the number tables, behind the blob in the image */
+    const __attribute__((address_space(3))) uint8_t *tabs =
+        (const __attribute__((address_space(3))) uint8_t *)(void *)s_fdesc + blob16;
+    const FastTabs tb{(const __attribute__((address_space(3))) uint64_t *)(tabs + FLI_P10U), (lds_f64 *)(tabs + FLI_P10D),
+                      (const __attribute__((address_space(3))) uint64_t *)(tabs + FLI_PW)};
     const dg_type rt = ldrec(&D.T[S.wrap ? S.wrap_inner : P.root]);
     const dg_struct sd = ldrec(&D.S[rt.st]);
     /* the key table: the name table's slots (read by phase 2, after phase 1's barrier) */
@@ -1383,6 +1403,8 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(D
     FLF_END();
 }
 
-void launch_flat_kernel(dim3 grid, hipStream_t s, const Params &P, const FlatParams &S); /* LDS: + the blob */
+void launch_flat_kernel(dim3 grid, hipStream_t s, const Params &P, const FlatParams &S); /* LDS: + the image */
+/* the image of blob[0, total_len) into img[0, fli_len(total_len)) (flat_image.hip) */
+void flat_image_build(const uint8_t *blob, uint32_t total_len, uint8_t *img);
 
 }  // namespace dg

@@ -198,9 +198,20 @@ static int desc_finish(dg_ctx *c, const dg_desc_hdr &h, DevArr<uint8_t> &d_blob,
 {
     if (h.magic != DG_DESC_MAGIC || h.version < 1 || h.version > DG_DESC_VERSION || h.total_len > len)
         return set_err(DG_E_DESC, "bad descriptor blob header");
+    /* the flat kernel's image, once per descriptor: the blob and the number
+     * tables as a block lays them out in LDS (flat_root's first two tests:
+     * other blobs never take that kernel) */
+    DevArr<uint8_t> d_flat;
+    if (h.version >= 2 && h.total_len <= FL_DESC) {
+        std::vector<uint8_t> img(fli_len(h.total_len));
+        flat_image_build((const uint8_t *)host_blob, h.total_len, img.data());
+        if (int rc = d_flat.alloc(img.size())) return rc;
+        HIPCHK(hipMemcpy(d_flat, img.data(), img.size(), hipMemcpyHostToDevice));
+    }
     dg_desc *d = new dg_desc();
     d->ctx = c;
     d->d_blob = std::move(d_blob);
+    d->d_flat = std::move(d_flat);
     d->len = len;
     d->hdr = h;
     d->hblob.assign((const uint8_t *)host_blob, (const uint8_t *)host_blob + h.total_len);
@@ -475,7 +486,7 @@ static int enqueue(dg_ctx *c, Scratch *x, const dg_desc *d, uint32_t root, const
         /* flat root struct: a lane group per message, a lane per field;
          * or a root whose messages wrap one flat struct (FlatParams::wrap) */
         FlatParams FP;
-        FP.blob = d->d_blob;
+        FP.img = d->d_flat;
         FP.hdr = d->hdr;
         FP.bail_count = cnt + CNT_BAIL;
         FP.bail_list = x->bail_list;

@@ -4,7 +4,7 @@
 namespace dg {
 void launch_flat_kernel(dim3 grid, hipStream_t s, const Params &P, const FlatParams &S)
 {
-    const uint32_t shmem = (S.hdr.total_len + 15) & ~15u;
+    const uint32_t shmem = fli_len(S.hdr.total_len);
     hipLaunchKernelGGL(j2t_flat_kernel<0>, grid, dim3(64 * FL_WAVES), shmem, s, P, S);
 }
 }  // namespace dg
