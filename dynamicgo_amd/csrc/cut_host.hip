@@ -92,18 +92,8 @@ static int cut_launch(dg_ctx *c, const dg_cut *pl, uint64_t opts, const CutBatch
     if (opts & ~(DG_CUT_WRITE_DEFAULT | DG_CUT_DISALLOW_UNKNOWN | DG_CUT_NOT_CHECK_REQ))
         return set_err(DG_E_INVALID, "unknown cut option bits %llx", (unsigned long long)opts);
     int rc;
-    if (!c->cut_cnt_buf) {
-        if ((rc = c->cut_cnt_buf.alloc(4))) return rc;
-        HIPCHK(hipMemset(c->cut_cnt_buf, 0, 16));
-        HIPCHK(hipDeviceSynchronize()); /* before a non-blocking stream counts on it */
-        c->cut_cnt.set[0] = c->cut_cnt_buf;
-        c->cut_cnt.set[1] = c->cut_cnt_buf + 1;
-        c->cut_cnt.bytes = 4;
-    }
-    if (c->cut_list.cap < n) { /* the previous launch may still fill the old list */
-        HIPCHK(c->cut.wait_host());
-        if ((rc = c->cut_list.grow(n))) return rc;
-    }
+    if (!c->cut_cnt_buf && (rc = c->cut_cnt.init(c->cut_cnt_buf, 1))) return rc;
+    if ((rc = c->cut.grow(c->cut_list, n))) return rc; /* the previous launch may still fill the old list */
     HIPCHK(c->cut.acquire(s));
     CutParams A;
     memset(&A, 0, sizeof A);
@@ -150,23 +140,12 @@ int dg_cut_create(dg_ctx *c, const void *blob, size_t len, dg_cut **out)
     std::unique_ptr<dg_cut> pl(new dg_cut());
     pl->ctx = c;
     pl->hdr = h;
-    if (int rc = pl->d_blob.alloc((size_t)h.total_len + 16)) return rc; /* literals are read 16 bytes at a time */
-    hipError_t e = hipMemcpy(pl->d_blob, blob, h.total_len, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(pl->d_blob + h.total_len, 0, 16);
-    if (e == hipSuccess) e = hipDeviceSynchronize(); /* before launches on non-blocking streams read it */
-    if (e != hipSuccess) return set_err(DG_E_HIP, "cut plan upload: %s", hipGetErrorString(e));
+    if (int rc = upload_blob(pl->d_blob, blob, h.total_len, "cut plan")) return rc;
     *out = pl.release();
     return DG_OK;
 }
 
-void dg_cut_destroy(dg_cut *p)
-{
-    if (!p) return;
-    Entry g(p->ctx, true);
-    p->d_blob.reset(); /* under the context lock, on its device */
-    g.lk.unlock();
-    delete p;
-}
+void dg_cut_destroy(dg_cut *p) { destroy_with_blob(p); }
 
 uint64_t dg_cut_slot_bound(const dg_cut *p, uint64_t len, uint64_t opts)
 {
@@ -192,68 +171,33 @@ int dg_cut_batch_host(dg_ctx *c, const dg_cut *pl, uint64_t opts, const uint8_t 
                       uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *out_off, uint64_t *ret, uint64_t *out_need)
 {
     if (!c || !pl || pl->ctx != c) return set_err(DG_E_INVALID, "null ctx/plan, or a plan of another context");
-    if (n == 0) {
-        if (out_off) out_off[0] = 0;
-        if (out_need) *out_need = 0;
-        return DG_OK;
-    }
+    if (n == 0) return empty_batch(out_off, out_need);
     if (!thrift || !in_off || !out_off || !ret) return set_err(DG_E_INVALID, "null buffer");
-    for (uint64_t i = 0; i < n; i++)
-        if (in_off[i + 1] < in_off[i]) return set_err(DG_E_INVALID, "in_off not ascending");
     Entry g(c, true);
     if (g.rc) return g.rc;
-    const hipStream_t s = g.s;
-    int rc;
-    std::vector<uint64_t> todo(n), where(n, 0);
-    std::vector<uint32_t> olen(n, 0);
+    /* what a pass downloads into is declared before the batch, whose destructor waits for the copies */
+    std::vector<uint64_t> todo, where(n, 0), po, r;
+    std::vector<uint32_t> olen(n, 0), l;
     std::vector<uint8_t> stage;
-    for (uint64_t i = 0; i < n; i++) todo[i] = i;
-    uint64_t max_len = 0;
-    for (uint64_t i = 0; i < n; i++) max_len = std::max<uint64_t>(max_len, in_off[i + 1] - in_off[i]);
-    for (int pass = 0; pass < 2 && !todo.empty(); pass++) {
-        const uint64_t m = todo.size();
-        std::vector<uint64_t> io(m + 1), so(m + 1), po(m + 1), r(m);
-        std::vector<uint32_t> l(m);
-        io[0] = so[0] = 0;
-        for (uint64_t k = 0; k < m; k++) {
-            const uint64_t i = todo[k], len = in_off[i + 1] - in_off[i];
-            io[k + 1] = io[k] + len;
-            const uint64_t cap = pass == 0 ? std::min(dg_cut_slot_bound(pl, len, opts), len + 256) : olen[i];
-            so[k + 1] = so[k] + ((cap + 15) & ~15ull); /* the packing reads its slots as aligned words */
-        }
-        if ((rc = c->d_json.grow(io[m] + 64)) || (rc = c->d_in_off.grow(m + 1)) || (rc = c->d_out.grow(so[m] + 64)) ||
-            (rc = c->d_out_off.grow(m + 1)) || (rc = c->d_out_len.grow(m + 1)) || (rc = c->d_ret.grow(m + 1)) ||
-            (rc = c->d_pack.grow(so[m] + 64)) || (rc = c->d_pack_off.grow(m + 1)))
+    HostBatch hb(c, g.s);
+    int rc;
+    for (int pass = 0; pass < 2 && (pass == 0 || !todo.empty()); pass++) {
+        const uint64_t m = pass ? todo.size() : n;
+        po.resize(m + 1), r.resize(m), l.resize(m);
+        if ((rc = hb.layout(in_off, pass ? todo.data() : nullptr, m, [&](uint64_t i, uint64_t len) -> uint64_t {
+                return pass == 0 ? std::min(dg_cut_slot_bound(pl, len, opts), len + 256) : olen[i];
+            })) ||
+            (rc = hb.upload_messages(thrift, in_off)) || (rc = hb.upload_slots()))
             return rc;
-        if (pass == 0) {
-            if (io[m]) HIPCHK(hipMemcpyAsync(c->d_json, thrift + in_off[0], io[m], hipMemcpyHostToDevice, s));
-        } else {
-            for (uint64_t k = 0; k < m; k++)
-                if (io[k + 1] > io[k])
-                    HIPCHK(hipMemcpyAsync(c->d_json + io[k], thrift + in_off[todo[k]], io[k + 1] - io[k],
-                                          hipMemcpyHostToDevice, s));
-        }
-        HIPCHK(hipMemsetAsync(c->d_json + io[m], 0, 64, s));
-        HIPCHK(hipMemcpyAsync(c->d_in_off, io.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_out_off, so.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
-        const CutBatch b{c->d_json, c->d_in_off, m, c->d_out, c->d_out_off, c->d_out_len, c->d_ret, max_len};
-        if ((rc = cut_launch(c, pl, opts, b, s))) return rc;
-        BatchArgs pb; /* what the packing reads; with ret, only status 0 packs */
-        pb.out = c->d_out, pb.out_off = c->d_out_off, pb.out_len = c->d_out_len, pb.ret = c->d_ret, pb.n = m;
-        if ((rc = dg_i_pack_scan(c, s, pb, c->d_pack, c->d_pack_off))) return rc;
-        HIPCHK(hipMemcpyAsync(r.data(), c->d_ret, m * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(l.data(), c->d_out_len, m * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(po.data(), c->d_pack_off, (m + 1) * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        const CutBatch b{c->d_json, c->d_in_off, m, c->d_out, c->d_out_off, c->d_out_len, c->d_ret, hb.max_len};
+        /* the packing goes by ret: only status 0 packs */
+        if ((rc = cut_launch(c, pl, opts, b, g.s)) || (rc = hb.pack(true, r.data(), po.data(), l.data()))) return rc;
         const uint64_t off0 = stage.size();
         stage.resize(off0 + po[m]);
-        if (po[m]) {
-            HIPCHK(hipMemcpyAsync(stage.data() + off0, c->d_pack, po[m], hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
+        if ((rc = hb.download(stage.data() + off0, c->d_pack, po[m]))) return rc;
         std::vector<uint64_t> next;
         for (uint64_t k = 0; k < m; k++) {
-            const uint64_t i = todo[k];
+            const uint64_t i = pass ? todo[k] : k;
             ret[i] = r[k];
             olen[i] = l[k];
             where[i] = off0 + po[k];

@@ -3,7 +3,8 @@
  * GPU resources (device and pinned arrays, events, streams), the rule that
  * orders a shared buffer across streams, the context, descriptor and
  * per-stream scratch records, the entry guard, the argument records of one
- * batch and the error helpers (j2t_host.hip defines the functions; t2j_host,
+ * batch, the host batch of the thrift/generic entries (HostBatch) and the
+ * error helpers (j2t_host.hip defines the functions; t2j_host,
  * tget_host, cut_host, edit_host, editm_host, kids_host and j2t_pipe use them).
  */
 #pragma once
@@ -19,6 +20,7 @@
 
 #include "../../include/dgj2t.h"
 #include "../../include/dgj2t_desc.h"
+#include "host_layout.h"
 
 __attribute__((visibility("hidden"))) int set_err(int code, const char *fmt, ...);
 #define HIPCHK(x)                                                                              \
@@ -144,6 +146,15 @@ struct StreamOrder {
     }
     /* the host waits for the last launch (before a buffer it may read goes) */
     hipError_t wait_host() const { return last ? hipEventSynchronize(done) : hipSuccess; }
+    /* grow a buffer it guards: the old one may still be used by the last
+     * launch, so wait for it before freeing */
+    template <class T>
+    int grow(DevArr<T> &a, uint64_t want)
+    {
+        if (a.cap >= want) return DG_OK;
+        HIPCHK(wait_host());
+        return a.grow(want);
+    }
     /* streams s[0..n) are about to be destroyed and the device is idle */
     void forget(const hipStream_t *s, int n)
     {
@@ -166,6 +177,15 @@ struct AltCounters {
     uint32_t bytes = 0, cur = 0;
     uint32_t *mine() const { return set[cur]; }
     uint32_t *other() const { return set[cur ^ 1u]; }
+    /* first use: the two sets, `words` counters each, in buf, zeroed */
+    int init(DevArr<uint32_t> &buf, uint32_t words)
+    {
+        if (int rc = buf.alloc(4)) return rc;
+        HIPCHK(hipMemset(buf, 0, 16));
+        HIPCHK(hipDeviceSynchronize()); /* before a non-blocking stream counts on it */
+        set[0] = buf, set[1] = buf + words, bytes = 4 * words;
+        return DG_OK;
+    }
     void finish(bool ok, hipStream_t s)
     {
         if (ok) cur ^= 1u;
@@ -236,15 +256,6 @@ struct Scratch : StreamOrder {
     {
         (void)wait_host();
         if (side) (void)hipStreamSynchronize(side);
-    }
-    /* grow a scratch buffer: the old one may still be read by the scratch's
-     * previous launch, so wait for it before freeing */
-    template <class T>
-    int grow(DevArr<T> &a, uint64_t want)
-    {
-        if (a.cap >= want) return DG_OK;
-        HIPCHK(wait_host());
-        return a.grow(want);
     }
 };
 
@@ -486,3 +497,190 @@ __attribute__((visibility("hidden"))) int dg_i_convert_pack(dg_ctx *c, const dg_
  * nothing */
 __attribute__((visibility("hidden"))) int dg_i_pack_scan(dg_ctx *c, hipStream_t s, const BatchArgs &b, uint8_t *d_dst,
                                                          uint64_t *d_dst_off);
+
+/* the answer of a host entry to n = 0 */
+inline int empty_batch(uint64_t *off, uint64_t *need)
+{
+    if (off) off[0] = 0;
+    if (need) *need = 0;
+    return DG_OK;
+}
+
+/* One batch of a thrift/generic host entry (tget, cut, edit, editm, kids), made
+ * after Entry: the layout (host_layout.h) in vectors it owns, their upload into
+ * the context's staging buffers, the packing and the download. Every copy is
+ * asynchronous on s and several read io / so / vo, so the destructor
+ * synchronises s when a copy was issued and no synchronise has followed it: an
+ * entry may return wherever it likes. What a download writes must be declared
+ * before the HostBatch (or be the caller's) for the same reason. */
+struct HostBatch {
+    dg_ctx *const c;
+    const hipStream_t s;
+    std::vector<uint64_t> io, so, vo, src; /* message, slot and value offsets; a gathering layout's sources */
+    uint64_t n = 0, max_len = 0;
+    bool busy = false; /* a copy may be in flight */
+    HostBatch(dg_ctx *c_, hipStream_t s_) : c(c_), s(s_) {}
+    HostBatch(const HostBatch &) = delete;
+    ~HostBatch()
+    {
+        if (busy) (void)hipStreamSynchronize(s);
+    }
+    int sync()
+    {
+        busy = false;
+        HIPCHK(hipStreamSynchronize(s));
+        return DG_OK;
+    }
+    int copy(void *dst, const void *from, uint64_t bytes, hipMemcpyKind kind)
+    {
+        busy = true;
+        if (bytes) HIPCHK(hipMemcpyAsync(dst, from, bytes, kind, s));
+        return DG_OK;
+    }
+    /* The layout of the messages idx[0..m) of the caller's in_off (idx null: of
+     * all m, which also sets max_len), each with a slot of cap_of(i, len)
+     * bytes when with_slots. A gather (idx) is of an in_off an earlier layout
+     * has checked. */
+    template <class F>
+    int layout(const uint64_t *in_off, const uint64_t *idx, uint64_t m, F cap_of, bool with_slots = true,
+               bool longest = true)
+    {
+        n = m, io.resize(m + 1), src.resize(idx ? m : 0);
+        if (with_slots) so.resize(m + 1);
+        uint64_t bad = 0, cap = 0;
+        const int rc = dg::hl_layout(in_off, idx, m, cap_of, io.data(), with_slots ? so.data() : nullptr,
+                                     idx ? src.data() : nullptr, longest && !idx ? &max_len : nullptr, &bad, &cap);
+        if (rc == dg::HL_DESCENDING) return set_err(DG_E_INVALID, "in_off not ascending");
+        if (rc) return set_err(DG_E_INVALID, "message %llu: an output of %llu bytes", (unsigned long long)bad,
+                               (unsigned long long)cap);
+        return DG_OK;
+    }
+    /* no slots: tget and kids write records; kids has no use for max_len either */
+    int messages(const uint64_t *in_off, uint64_t m, bool longest = true)
+    {
+        return layout(in_off, nullptr, m, [](uint64_t, uint64_t) { return uint64_t(0); }, false, longest);
+    }
+    /* vo[m K + 1] and max_val[K] from the val_off of m messages, message-major */
+    int values(const uint64_t *val_off, uint64_t m, uint64_t K, uint64_t *max_val)
+    {
+        vo.resize(m * K + 1);
+        return dg::hl_rebase(val_off, m * K, K, vo.data(), max_val) ? set_err(DG_E_INVALID, "val_off not ascending") : DG_OK;
+    }
+    /* d_json: the messages and 64 zero bytes, d_in_off: io. The arena in one
+     * copy from in_off[0], or after a gathering layout message by message. */
+    int upload_messages(const uint8_t *thrift, const uint64_t *in_off)
+    {
+        int rc;
+        if ((rc = c->d_json.grow(io[n] + 64)) || (rc = c->d_in_off.grow(n + 1))) return rc;
+        if (src.empty()) rc = copy(c->d_json, thrift + in_off[0], io[n], hipMemcpyHostToDevice);
+        for (uint64_t k = 0; k < src.size() && !rc; k++)
+            rc = copy(c->d_json + io[k], thrift + src[k], io[k + 1] - io[k], hipMemcpyHostToDevice);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(c->d_json + io[n], 0, 64, s));
+        return copy(c->d_in_off, io.data(), (n + 1) * 8, hipMemcpyHostToDevice);
+    }
+    /* the output side: the slots, their lengths and status words, the packing */
+    int upload_slots()
+    {
+        int rc;
+        if ((rc = c->d_out.grow(so[n] + 64)) || (rc = c->d_out_off.grow(n + 1)) || (rc = c->d_out_len.grow(n + 1)) ||
+            (rc = c->d_ret.grow(n + 1)) || (rc = c->d_pack.grow(so[n] + 64)) || (rc = c->d_pack_off.grow(n + 1)))
+            return rc;
+        return copy(c->d_out_off, so.data(), (n + 1) * 8, hipMemcpyHostToDevice);
+    }
+    /* d_cb: the values and 64 zero bytes. With val_off (after values()) those
+     * it spans and d_aux: vo; without, val[0, shared) for every message */
+    int upload_values(const uint8_t *val, const uint64_t *val_off, uint64_t shared)
+    {
+        const uint64_t vtotal = val_off ? vo.back() : shared;
+        int rc;
+        if ((rc = c->d_cb.grow(vtotal + 64)) || (rc = c->d_aux.grow(vo.size())) ||
+            (rc = copy(c->d_cb, val_off ? val + val_off[0] : val, vtotal, hipMemcpyHostToDevice)))
+            return rc;
+        HIPCHK(hipMemsetAsync(c->d_cb + vtotal, 0, 64, s));
+        return copy(c->d_aux, vo.data(), vo.size() * 8, hipMemcpyHostToDevice);
+    }
+    /* the slots packed into d_pack / d_pack_off: by the lengths, or with by_ret
+     * only the messages of status 0; then the status words, the packed
+     * offsets and (optional) the lengths on the host */
+    int pack(bool by_ret, uint64_t *ret, uint64_t *pack_off, uint32_t *len = nullptr)
+    {
+        BatchArgs pb;
+        pb.out = c->d_out, pb.out_off = c->d_out_off, pb.out_len = c->d_out_len, pb.n = n;
+        if (by_ret) pb.ret = c->d_ret;
+        int rc;
+        if ((rc = dg_i_pack_scan(c, s, pb, c->d_pack, c->d_pack_off)) ||
+            (rc = copy(ret, c->d_ret, n * 8, hipMemcpyDeviceToHost)) ||
+            (len && (rc = copy(len, c->d_out_len, n * 4, hipMemcpyDeviceToHost))) ||
+            (rc = copy(pack_off, c->d_pack_off, (n + 1) * 8, hipMemcpyDeviceToHost)))
+            return rc;
+        return sync();
+    }
+    int download(void *dst, const void *d_from, uint64_t bytes)
+    {
+        if (int rc = copy(dst, d_from, bytes, hipMemcpyDeviceToHost)) return rc;
+        return bytes ? sync() : DG_OK;
+    }
+    /* the packing goes by the lengths: 0 for every failed message (no slot can overflow) */
+    int pack_and_download(const HostOut &o, uint64_t *ret)
+    {
+        if (int rc = pack(false, ret, o.out_off)) return rc;
+        const uint64_t total = o.out_off[n];
+        if (o.out_need) *o.out_need = total;
+        if (total > o.out_cap || (!o.out && total))
+            return set_err(DG_E_NOMEM, "output needs %llu bytes", (unsigned long long)total);
+        return download(o.out, c->d_pack, total);
+    }
+};
+
+/* a plan's blob on the device with 16 zero bytes after it (keys and literals
+ * are read 16 bytes at a time) */
+inline int upload_blob(DevArr<uint8_t> &d, const void *blob, size_t len, const char *what)
+{
+    if (int rc = d.alloc(len + 16)) return rc;
+    hipError_t e = hipMemcpy(d, blob, len, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d + len, 0, 16);
+    if (e == hipSuccess) e = hipDeviceSynchronize(); /* before launches on non-blocking streams read it */
+    if (e != hipSuccess) return set_err(DG_E_HIP, "%s upload: %s", what, hipGetErrorString(e));
+    return DG_OK;
+}
+
+/* the end of a dg_path or dg_cut: its blob goes under the context lock, on its device */
+template <class P>
+void destroy_with_blob(P *p)
+{
+    if (!p) return;
+    {
+        Entry g(p->ctx, true);
+        p->d_blob.reset();
+    }
+    delete p;
+}
+
+/* what a SET can add to a message besides the value, by the last step's kind */
+inline uint32_t edit_step_extra(uint32_t kind, uint32_t key_len)
+{
+    return kind == DG_PS_FIELD ? 3u : kind == DG_PS_INDEX ? 0u : kind == DG_PS_STRKEY ? 4u + key_len
+           : kind == DG_PS_BINKEY ? key_len : 8u;
+}
+
+/* The splice of edit and editm: lane(lanes per message), then wave(blocks of
+ * `waves` waves, a message each). A route no message can take is not launched:
+ * the lane route when edit_wave_min is 0, the wave route when the caller's
+ * hints bound every output below edit_wave_min (no_wave). */
+template <class Lane, class Wave>
+hipError_t launch_splice_routes(const dg_ctx *c, uint64_t n, uint32_t waves, bool no_wave, Lane lane, Wave wave)
+{
+    hipError_t err = hipSuccess;
+    if (c->knobs.edit_wave_min > 0) {
+        const int64_t g = c->knobs.edit_lanes;
+        lane(g == 4 || g == 16 ? (uint32_t)g : 1u);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess && !no_wave) {
+        const uint64_t want = (n + waves - 1) / waves;
+        wave((uint32_t)std::min<uint64_t>(want, (uint64_t)c->n_cu * 8));
+        err = hipGetLastError();
+    }
+    return err;
+}

@@ -38,19 +38,10 @@ static int kids_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t
     if (n > 0xFFFFFFFFull) return set_err(DG_E_INVALID, "batch of %llu messages", (unsigned long long)n);
     if (flags & ~(DG_KIDS_F_RECURSE | DG_KIDS_F_COUNTED)) return set_err(DG_E_INVALID, "unknown flags %x", flags);
     int rc;
-    if (!c->kids.ws) {
-        if ((rc = c->kids.ws.alloc(KIDS_WS)) || (rc = c->kids_cnt_buf.alloc(4))) return rc;
-        HIPCHK(hipMemset(c->kids_cnt_buf, 0, 16));
-        HIPCHK(hipDeviceSynchronize()); /* before a non-blocking stream counts on it */
-        c->kids_cnt.set[0] = c->kids_cnt_buf;
-        c->kids_cnt.set[1] = c->kids_cnt_buf + 2;
-        c->kids_cnt.bytes = 8;
-    }
-    const uint64_t tiles = (n + KD_SCAN_TILE - 1) / KD_SCAN_TILE;
-    if (c->kids_list.cap < 2 * n || c->kids_sums.cap < tiles) { /* the previous launch may still use the old ones */
-        HIPCHK(c->kids.wait_host());
-        if ((rc = c->kids_list.grow(2 * n)) || (rc = c->kids_sums.grow(tiles))) return rc;
-    }
+    if (!c->kids.ws && ((rc = c->kids.ws.alloc(KIDS_WS)) || (rc = c->kids_cnt.init(c->kids_cnt_buf, 2)))) return rc;
+    /* the previous launch may still use the old queues and tile sums */
+    if ((rc = c->kids.grow(c->kids_list, 2 * n)) || (rc = c->kids.grow(c->kids_sums, (n + KD_SCAN_TILE - 1) / KD_SCAN_TILE)))
+        return rc;
     HIPCHK(c->kids.acquire(s));
     KDParams A;
     memset(&A, 0, sizeof A);
@@ -112,36 +103,22 @@ int dg_kids_batch_host(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t
 {
     if (int rc = kids_args(c, ps)) return rc;
     if (flags & DG_KIDS_F_COUNTED) return set_err(DG_E_INVALID, "DG_KIDS_F_COUNTED is the device entry's");
-    if (n == 0) {
-        if (rec_off) rec_off[0] = 0;
-        if (need) *need = 0;
-        return DG_OK;
-    }
+    if (n == 0) return empty_batch(rec_off, need);
     if (!thrift || !in_off || !head || !rec_off) return set_err(DG_E_INVALID, "null buffer");
-    std::vector<uint64_t> io(n + 1);
-    const uint64_t base = in_off[0];
-    for (uint64_t i = 0; i <= n; i++) {
-        if (in_off[i] < base || (i && in_off[i] < in_off[i - 1])) return set_err(DG_E_INVALID, "in_off not ascending");
-        io[i] = in_off[i] - base;
-    }
-    const uint64_t total = io[n];
     Entry g(c, true);
     if (g.rc) return g.rc;
     const hipStream_t s = g.s;
+    HostBatch hb(c, s);
     int rc;
-    if ((rc = c->d_json.grow(total + 64)) || (rc = c->d_in_off.grow(n + 1)) || (rc = c->d_aux.grow(2 * n + 2)) ||
-        (rc = c->d_ret.grow(n + 1)))
+    if ((rc = hb.messages(in_off, n, false)) || (rc = c->d_aux.grow(2 * n + 2)) || (rc = c->d_ret.grow(n + 1)) ||
+        (rc = hb.upload_messages(thrift, in_off)))
         return rc;
-    if (total) HIPCHK(hipMemcpyAsync(c->d_json, thrift + base, total, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(c->d_json + total, 0, 64, s));
-    HIPCHK(hipMemcpyAsync(c->d_in_off, io.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s)); /* io is a local */
     dg_kids_head *d_head = (dg_kids_head *)(void *)c->d_aux.p;
     KidsBatch b{c->d_json, c->d_in_off, n, d_head, c->d_ret, nullptr, 0};
-    if ((rc = kids_launch(c, ps, root_type, flags, b, s))) return rc; /* count and scan */
-    HIPCHK(hipMemcpyAsync(rec_off, c->d_ret, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(head, d_head, n * sizeof(dg_kids_head), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = kids_launch(c, ps, root_type, flags, b, s)) || /* count and scan */
+        (rc = hb.copy(rec_off, c->d_ret, (n + 1) * 8, hipMemcpyDeviceToHost)) ||
+        (rc = hb.download(head, d_head, n * sizeof(dg_kids_head))))
+        return rc;
     const uint64_t want = rec_off[n];
     if (need) *need = want;
     if (!recs && !rec_cap) return DG_OK; /* sizing */
@@ -150,9 +127,7 @@ int dg_kids_batch_host(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t
     if ((rc = c->d_out.grow(want * sizeof(dg_kid_rec) + 64))) return rc;
     b.recs = (dg_kid_rec *)(void *)c->d_out.p, b.rec_cap = want;
     if ((rc = kids_launch(c, ps, root_type, flags | DG_KIDS_F_COUNTED, b, s))) return rc;
-    HIPCHK(hipMemcpyAsync(recs, c->d_out, want * sizeof(dg_kid_rec), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return DG_OK;
+    return hb.download(recs, c->d_out, want * sizeof(dg_kid_rec));
 }
 
 }  // extern "C"

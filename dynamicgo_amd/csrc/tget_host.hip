@@ -42,18 +42,8 @@ int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const TGetBatch
     if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
         return set_err(DG_E_INVALID, "batch of %llu messages x %u paths", (unsigned long long)n, ps->hdr.n_paths);
     int rc;
-    if (!c->tget.ws) {
-        if ((rc = c->tget.ws.alloc(TGET_WS)) || (rc = c->tget_cnt_buf.alloc(4))) return rc;
-        HIPCHK(hipMemset(c->tget_cnt_buf, 0, 16));
-        HIPCHK(hipDeviceSynchronize()); /* before a non-blocking stream counts on it */
-        c->tget_cnt.set[0] = c->tget_cnt_buf;
-        c->tget_cnt.set[1] = c->tget_cnt_buf + 1;
-        c->tget_cnt.bytes = 4;
-    }
-    if (c->tget_list.cap < pairs) { /* the previous launch may still fill the old list */
-        HIPCHK(c->tget.wait_host());
-        if ((rc = c->tget_list.grow(pairs))) return rc;
-    }
+    if (!c->tget.ws && ((rc = c->tget.ws.alloc(TGET_WS)) || (rc = c->tget_cnt.init(c->tget_cnt_buf, 1)))) return rc;
+    if ((rc = c->tget.grow(c->tget_list, pairs))) return rc; /* the previous launch may still fill the old list */
     HIPCHK(c->tget.acquire(s));
     TGParams A;
     memset(&A, 0, sizeof A);
@@ -134,23 +124,12 @@ int dg_path_create(dg_ctx *c, const void *blob, size_t len, dg_path **out)
     std::unique_ptr<dg_path> ps(new dg_path());
     ps->ctx = c;
     ps->hdr = h;
-    if (int rc = ps->d_blob.alloc((size_t)h.total_len + 16)) return rc; /* keys are compared 16 bytes at a time */
-    hipError_t e = hipMemcpy(ps->d_blob, blob, h.total_len, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(ps->d_blob + h.total_len, 0, 16);
-    if (e == hipSuccess) e = hipDeviceSynchronize(); /* before launches on non-blocking streams read it */
-    if (e != hipSuccess) return set_err(DG_E_HIP, "path upload: %s", hipGetErrorString(e));
+    if (int rc = upload_blob(ps->d_blob, blob, h.total_len, "path")) return rc;
     *out = ps.release();
     return DG_OK;
 }
 
-void dg_path_destroy(dg_path *p)
-{
-    if (!p) return;
-    Entry g(p->ctx, true);
-    p->d_blob.reset(); /* under the context lock, on its device */
-    g.lk.unlock();
-    delete p;
-}
+void dg_path_destroy(dg_path *p) { destroy_with_blob(p); }
 
 uint32_t dg_path_count(const dg_path *p) { return p ? p->hdr.n_paths : 0; }
 
@@ -171,28 +150,14 @@ int dg_tget_batch_host(dg_ctx *c, const dg_path *ps, uint8_t root_type, const ui
     if (!thrift || !in_off || !rec) return set_err(DG_E_INVALID, "null buffer");
     Entry g(c, true);
     if (g.rc) return g.rc;
-    const uint64_t base = in_off[0], total = in_off[n] - base, pairs = n * ps->hdr.n_paths;
-    std::vector<uint64_t> io(n + 1);
-    uint64_t max_len = 0;
-    for (uint64_t i = 0; i <= n; i++) {
-        if (in_off[i] < base || (i && in_off[i] < in_off[i - 1])) return set_err(DG_E_INVALID, "in_off not ascending");
-        io[i] = in_off[i] - base;
-        if (i) max_len = std::max<uint64_t>(max_len, io[i] - io[i - 1]);
-    }
+    const uint64_t rec_bytes = n * ps->hdr.n_paths * sizeof(dg_tget_rec);
+    HostBatch hb(c, g.s);
     int rc;
-    const hipStream_t s = g.s;
-    if ((rc = c->d_json.grow(total + 64))) return rc;
-    if ((rc = c->d_in_off.grow(n + 1))) return rc;
-    if ((rc = c->d_out.grow(pairs * sizeof(dg_tget_rec) + 64))) return rc;
-    if (total) HIPCHK(hipMemcpyAsync(c->d_json, thrift + base, total, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(c->d_json + total, 0, 64, s));
-    HIPCHK(hipMemcpyAsync(c->d_in_off, io.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s)); /* io is a local */
-    const TGetBatch b{c->d_json, c->d_in_off, n, (dg_tget_rec *)(void *)c->d_out, nullptr, nullptr, max_len};
-    if ((rc = tget_launch(c, ps, root_type, b, s))) return rc;
-    HIPCHK(hipMemcpyAsync(rec, c->d_out, pairs * sizeof(dg_tget_rec), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return DG_OK;
+    if ((rc = hb.messages(in_off, n)) || (rc = c->d_out.grow(rec_bytes + 64)) || (rc = hb.upload_messages(thrift, in_off)))
+        return rc;
+    const TGetBatch b{c->d_json, c->d_in_off, n, (dg_tget_rec *)(void *)c->d_out, nullptr, nullptr, hb.max_len};
+    if ((rc = tget_launch(c, ps, root_type, b, g.s))) return rc;
+    return hb.download(rec, c->d_out, rec_bytes);
 }
 
 }  // extern "C"

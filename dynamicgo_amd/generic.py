@@ -19,6 +19,7 @@ decoded; a result is the sub-value's byte span and wire type.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import struct
 from typing import List, Optional, Sequence
@@ -146,8 +147,58 @@ def compile_paths(paths: Sequence[Sequence[Path]], desc=None) -> bytes:
     return hdr + bytes(ents) + b"\0" * (off_steps - 32 - len(ents)) + bytes(steps) + bytes(pool)
 
 
-class PathSet:
+class _Handle:
+    """What the plan classes share: .h, a handle of the library that
+    close() gives to the function named _destroy, and `with`."""
+    _destroy = None
+    h = None
+
+    def close(self):
+        if self.h:
+            getattr(_lib.lib(), self._destroy)(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+@contextlib.contextmanager
+def _unless_given(made, given):
+    """Closes `made` after the block unless it is the caller's own `given`."""
+    try:
+        yield
+    finally:
+        if made is not given:
+            made.close()
+
+
+def _arena(msgs):
+    """(arena, in_off) of a non-empty batch: the messages back to back with 16
+    spare bytes, and uint64[n + 1] offsets from 0."""
+    n = len(msgs)
+    in_off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n), out=in_off[1:])
+    return np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8), in_off
+
+
+def _until_fits(call, cap: int, need):
+    """call(cap) -> (rc, out) with room for `cap`; on DG_E_NOMEM (-3) with a
+    larger *need, once more at that size. Returns the out that fitted."""
+    while True:
+        rc, out = call(cap)
+        if rc == -3 and need.value > cap:
+            cap = int(need.value)
+            continue
+        _lib.check(rc)
+        return out
+
+
+class PathSet(_Handle):
     """A compiled path set on one context's device (dg_path)."""
+    _destroy = "dg_path_destroy"
 
     def __init__(self, paths, desc=None, ctx: Optional[Context] = None):
         self.ctx = ctx or default_context()
@@ -156,17 +207,6 @@ class PathSet:
         _lib.check(_lib.lib().dg_path_create(self.ctx.h, bytes(self.blob), len(self.blob), C.byref(h)))
         self.h = h
         self.count = int(_lib.lib().dg_path_count(h))
-
-    def close(self):
-        if self.h:
-            _lib.lib().dg_path_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 class Result:
@@ -192,22 +232,16 @@ def get_by_path_records(msgs: Sequence[bytes], paths, desc=None, root_type: int 
                         ctx: Optional[Context] = None) -> np.ndarray:
     """The records of dg_tget_batch_host as a (len(msgs), P) array of REC_DTYPE."""
     ps = paths if isinstance(paths, PathSet) else PathSet(paths, desc, ctx)
-    try:
+    with _unless_given(ps, paths):
         n = len(msgs)
         rec = np.zeros((n, ps.count), dtype=REC_DTYPE)
         if n == 0:
             _lib.check(_lib.lib().dg_tget_batch_host(ps.ctx.h, ps.h, root_type, None, None, 0, None))
             return rec
-        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-        in_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens, out=in_off[1:])
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        arena, in_off = _arena(msgs)
         _lib.check(_lib.lib().dg_tget_batch_host(ps.ctx.h, ps.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
                                                  rec.ctypes.data))
         return rec
-    finally:
-        if ps is not paths:
-            ps.close()
 
 
 def get_by_path_batch(msgs: Sequence[bytes], paths, desc=None, root_type: int = STRUCT,
@@ -224,6 +258,15 @@ def _ptr(x) -> Optional[int]:
     return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
 
 
+def _stream_handle(stream, thrift):
+    """A torch stream, a raw stream handle, or None for torch's current stream
+    when `thrift` is a tensor -> the raw handle."""
+    if stream is None and hasattr(thrift, "device"):
+        import torch
+        stream = torch.cuda.current_stream(thrift.device)
+    return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+
 def get_by_path_device(paths: PathSet, thrift, in_off, n: int, rec, val_off=None, val_len=None,
                        root_type: int = STRUCT, stream=None, max_len: int = 0):
     """Device-resident batch (dg_tget_batch_device) over torch tensors or raw
@@ -232,10 +275,7 @@ def get_by_path_device(paths: PathSet, thrift, in_off, n: int, rec, val_off=None
     int64[n * P] and val_len int32[n * P] optional (what dg_pack_device_scan
     takes). Asynchronous on `stream` (a torch stream, a raw stream handle, or
     None for torch's current stream when `thrift` is a tensor)."""
-    if stream is None and hasattr(thrift, "device"):
-        import torch
-        stream = torch.cuda.current_stream(thrift.device)
-    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    s = _stream_handle(stream, thrift)
     _lib.check(_lib.lib().dg_tget_batch_device(paths.ctx.h, paths.h, root_type, _ptr(thrift), _ptr(in_off), n, _ptr(rec),
                                                _ptr(val_off), _ptr(val_len), s, max_len))
 
@@ -416,8 +456,9 @@ def _cut_word(opts) -> int:
     return 0 if opts is None else opts.word() if hasattr(opts, "word") else int(opts)
 
 
-class CutPlan:
+class CutPlan(_Handle):
     """A compiled cut plan on one context's device (dg_cut)."""
+    _destroy = "dg_cut_destroy"
 
     def __init__(self, from_desc, to_desc=None, ctx: Optional[Context] = None):
         self.ctx = ctx or default_context()
@@ -428,17 +469,6 @@ class CutPlan:
 
     def slot_bound(self, length: int, opts=None) -> int:
         return int(_lib.lib().dg_cut_slot_bound(self.h, length, _cut_word(opts)))
-
-    def close(self):
-        if self.h:
-            _lib.lib().dg_cut_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 class CutResult:
@@ -463,33 +493,24 @@ def marshal_to_batch(msgs: Sequence[bytes], from_desc, to_desc=None, opts=None,
     msgs[i], written under from_desc, cut to to_desc. from_desc may be a
     CutPlan (to_desc is then unused). Descriptor sameness: same_descriptor."""
     plan = from_desc if isinstance(from_desc, CutPlan) else CutPlan(from_desc, to_desc, ctx)
-    try:
+    with _unless_given(plan, from_desc):
         n = len(msgs)
         L = _lib.lib()
         if n == 0:
             _lib.check(L.dg_cut_batch_host(plan.ctx.h, plan.h, _cut_word(opts), None, None, 0, None, 0, None, None, None))
             return []
-        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-        in_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens, out=in_off[1:])
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        arena, in_off = _arena(msgs)
         out_off = np.zeros(n + 1, dtype=np.uint64)
         ret = np.zeros(n, dtype=np.uint64)
         need = C.c_uint64(0)
-        cap = int(in_off[n]) + 4096
-        while True:
+
+        def call(cap):
             out = np.zeros(cap, dtype=np.uint8)
-            rc = L.dg_cut_batch_host(plan.ctx.h, plan.h, _cut_word(opts), arena.ctypes.data, in_off.ctypes.data, n,
-                                     out.ctypes.data, cap, out_off.ctypes.data, ret.ctypes.data, C.byref(need))
-            if rc == -3 and need.value > cap:  # DG_E_NOMEM: the literals outgrew the guess
-                cap = int(need.value)
-                continue
-            _lib.check(rc)
-            break
+            return L.dg_cut_batch_host(plan.ctx.h, plan.h, _cut_word(opts), arena.ctypes.data, in_off.ctypes.data, n,
+                                       out.ctypes.data, cap, out_off.ctypes.data, ret.ctypes.data, C.byref(need)), out
+
+        out = _until_fits(call, int(in_off[n]) + 4096, need)  # a guess the literals may outgrow
         return [CutResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes()) for i in range(n)]
-    finally:
-        if plan is not from_desc:
-            plan.close()
 
 
 def marshal_to_device(plan: CutPlan, thrift, in_off, n: int, out, out_off, out_len, ret, opts=None, stream=None,
@@ -501,10 +522,7 @@ def marshal_to_device(plan: CutPlan, thrift, in_off, n: int, out, out_off, out_l
     ret int64[n] (status | aux << 32). out must not alias thrift. Asynchronous
     on `stream` (a torch stream, a raw stream handle, or None for torch's
     current stream when `thrift` is a tensor)."""
-    if stream is None and hasattr(thrift, "device"):
-        import torch
-        stream = torch.cuda.current_stream(thrift.device)
-    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    s = _stream_handle(stream, thrift)
     _lib.check(_lib.lib().dg_cut_batch_device(plan.ctx.h, plan.h, _cut_word(opts), _ptr(thrift), _ptr(in_off), n, _ptr(out),
                                               _ptr(out_off), _ptr(out_len), _ptr(ret), s, max_len))
 
@@ -522,7 +540,7 @@ EDIT_ERROR_NAMES = {EDIT_OK: None, EDIT_NOT_FOUND: "ErrNotFound", EDIT_E_READ: "
                     EDIT_E_TYPE: "ErrDismatchType", EDITM_E_SAME: "ErrSame", EDIT_E_OVERFLOW: "ErrOverflow"}
 
 
-class EditPlan:
+class EditPlan(_Handle):
     """One edit on one context's device (dg_edit): ONE path of at least one
     step (a list of Path steps; PathFieldName is resolved through `desc` by
     compile_paths) and an op, EDIT_SET or EDIT_UNSET. `path` may also be the
@@ -553,6 +571,7 @@ class EditPlan:
          the C ABI.
     Several children of one node in one pass: EditManyPlan (SetMany). Items
     under different parents stay a second edit on the first one's output."""
+    _destroy = "dg_edit_destroy"
 
     def __init__(self, path, op: int, desc=None, ctx: Optional[Context] = None):
         self.op = int(op)
@@ -570,17 +589,6 @@ class EditPlan:
     def slot_bound(self, length: int, val_len: int = 0) -> int:
         """The exact worst case of one message's output (dg_edit_slot_bound)."""
         return int(_lib.lib().dg_edit_slot_bound(self.h, length, val_len))
-
-    def close(self):
-        if self.h:
-            _lib.lib().dg_edit_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 class EditResult:
@@ -609,38 +617,30 @@ def _edit_batch(msgs, plan: EditPlan, values, val_type: int, root_type: int) -> 
         _lib.check(L.dg_edit_batch_host(plan.ctx.h, plan.h, root_type, None, None, 0, val_type, None, None, 0, None, 0,
                                         None, None, None))
         return []
-    lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-    in_off = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum(lens, out=in_off[1:])
-    arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+    arena, in_off = _arena(msgs)
     val = val_off = None
     val_len = vtotal = 0
     if values is not None:
         if isinstance(values, (bytes, bytearray)):
             val = np.frombuffer(bytes(values) + b"\0" * 16, dtype=np.uint8)
-            val_len = vtotal = len(values)
+            val_len = len(values)
         else:
             if len(values) != n:
                 raise ValueError("%d values for %d messages" % (len(values), n))
-            val_off = np.zeros(n + 1, dtype=np.uint64)
-            np.cumsum(np.fromiter((len(v) for v in values), dtype=np.uint64, count=n), out=val_off[1:])
-            val = np.frombuffer(b"".join(bytes(v) for v in values) + b"\0" * 16, dtype=np.uint8)
+            val, val_off = _arena([bytes(v) for v in values])
             vtotal = int(val_off[n])
     out_off = np.zeros(n + 1, dtype=np.uint64)
     ret = np.zeros(n, dtype=np.uint64)
     need = C.c_uint64(0)
-    cap = int(in_off[n]) + (vtotal if val_off is not None else 0)  # a guess; the call says what it needs
-    while True:
+
+    def call(cap):
         out = np.zeros(max(cap, 1), dtype=np.uint8)
-        rc = L.dg_edit_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n, val_type,
-                                  None if val is None else val.ctypes.data,
-                                  None if val_off is None else val_off.ctypes.data, val_len, out.ctypes.data, cap,
-                                  out_off.ctypes.data, ret.ctypes.data, C.byref(need))
-        if rc == -3 and need.value > cap:  # DG_E_NOMEM: the inserts outgrew the guess
-            cap = int(need.value)
-            continue
-        _lib.check(rc)
-        break
+        return L.dg_edit_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n, val_type,
+                                    None if val is None else val.ctypes.data,
+                                    None if val_off is None else val_off.ctypes.data, val_len, out.ctypes.data, cap,
+                                    out_off.ctypes.data, ret.ctypes.data, C.byref(need)), out
+
+    out = _until_fits(call, int(in_off[n]) + vtotal, need)  # a guess the inserts may outgrow
     return [EditResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes()) for i in range(n)]
 
 
@@ -652,13 +652,10 @@ def set_by_path_batch(msgs: Sequence[bytes], path, values, val_type: int, desc=N
     message: the value's Thrift-binary bytes, taken as given, of wire type
     val_type. Semantics and the deviations from the reference: EditPlan."""
     plan = path if isinstance(path, EditPlan) else EditPlan(path, EDIT_SET, desc, ctx)
-    try:
+    with _unless_given(plan, path):
         if plan.op != EDIT_SET:
             raise ValueError("set_by_path_batch needs an EDIT_SET plan")
         return _edit_batch(msgs, plan, values, val_type, root_type)
-    finally:
-        if plan is not path:
-            plan.close()
 
 
 def unset_by_path_batch(msgs: Sequence[bytes], path, desc=None, root_type: int = STRUCT,
@@ -667,13 +664,10 @@ def unset_by_path_batch(msgs: Sequence[bytes], path, desc=None, root_type: int =
     entry at `path` (a list of Path steps, or an EditPlan of op EDIT_UNSET) is
     dropped. Semantics and the deviations from the reference: EditPlan."""
     plan = path if isinstance(path, EditPlan) else EditPlan(path, EDIT_UNSET, desc, ctx)
-    try:
+    with _unless_given(plan, path):
         if plan.op != EDIT_UNSET:
             raise ValueError("unset_by_path_batch needs an EDIT_UNSET plan")
         return _edit_batch(msgs, plan, None, 0, root_type)
-    finally:
-        if plan is not path:
-            plan.close()
 
 
 def edit_device(plan: EditPlan, thrift, in_off, n: int, val_type: int, val, val_off, out, out_off, out_len, ret,
@@ -689,10 +683,7 @@ def edit_device(plan: EditPlan, thrift, in_off, n: int, val_type: int, val, val_
     when given, must not be less than the longest message. Asynchronous on
     `stream` (a torch stream, a raw stream handle, or None for torch's current
     stream when `thrift` is a tensor)."""
-    if stream is None and hasattr(thrift, "device"):
-        import torch
-        stream = torch.cuda.current_stream(thrift.device)
-    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    s = _stream_handle(stream, thrift)
     _lib.check(_lib.lib().dg_edit_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n, val_type,
                                                _ptr(val), _ptr(val_off), val_len, _ptr(out), _ptr(out_off),
                                                _ptr(out_len), _ptr(ret), s, max_len))
@@ -709,7 +700,7 @@ def _step_class(kind: int) -> int:
     return 0 if kind == PS_FIELD else 1 if kind == PS_INDEX else 2
 
 
-class EditManyPlan:
+class EditManyPlan(_Handle):
     """One many-edit on one context's device (dg_editm): a `parent` path of 0
     to 15 steps, 1 to 7 last `steps` below it and an op. Every step is one
     Path; all are of one class: all fields (PathFieldId / PathFieldName,
@@ -732,6 +723,7 @@ class EditManyPlan:
          legal double insert;
       10. mixed step classes are refused: ValueError here, DG_E_ARG in the C
           ABI."""
+    _destroy = "dg_editm_destroy"
 
     def __init__(self, parent, steps, op: int, desc=None, ctx: Optional[Context] = None):
         self.op = int(op)
@@ -752,17 +744,6 @@ class EditManyPlan:
         """The exact worst case of one message's output (dg_editm_slot_bound);
         val_total: the K values' lengths together."""
         return int(_lib.lib().dg_editm_slot_bound(self.h, length, val_total))
-
-    def close(self):
-        if self.h:
-            _lib.lib().dg_editm_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 class EditManyResult:
@@ -795,10 +776,7 @@ def _editm_batch(msgs, plan: EditManyPlan, values, val_types, root_type: int) ->
         _lib.check(L.dg_editm_batch_host(plan.ctx.h, plan.h, root_type, None, None, 0, vt.ctypes.data, None, None,
                                          vl.ctypes.data, None, 0, None, None, None))
         return []
-    lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-    in_off = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum(lens, out=in_off[1:])
-    arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+    arena, in_off = _arena(msgs)
     val = val_off = None
     vtotal = 0
     if values is not None:
@@ -809,26 +787,21 @@ def _editm_batch(msgs, plan: EditManyPlan, values, val_types, root_type: int) ->
             for v in values:
                 if not isinstance(v, (bytes, bytearray)) and len(v) != n:
                     raise ValueError("%d values for %d messages" % (len(v), n))
-            flat = [bytes(v) if isinstance(v, (bytes, bytearray)) else bytes(v[i]) for i in range(n) for v in values]
-            val_off = np.zeros(n * k + 1, dtype=np.uint64)
-            np.cumsum(np.fromiter((len(v) for v in flat), dtype=np.uint64, count=n * k), out=val_off[1:])
-            val = np.frombuffer(b"".join(flat) + b"\0" * 16, dtype=np.uint8)
+            val, val_off = _arena([bytes(v) if isinstance(v, (bytes, bytearray)) else bytes(v[i])
+                                   for i in range(n) for v in values])
             vtotal = int(val_off[n * k])
     out_off = np.zeros(n + 1, dtype=np.uint64)
     ret = np.zeros(n, dtype=np.uint64)
     need = C.c_uint64(0)
-    cap = int(in_off[n]) + vtotal  # a guess; the call says what it needs
-    while True:
+
+    def call(cap):
         out = np.zeros(max(cap, 1), dtype=np.uint8)
-        rc = L.dg_editm_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
-                                   vt.ctypes.data, None if val is None else val.ctypes.data,
-                                   None if val_off is None else val_off.ctypes.data, vl.ctypes.data, out.ctypes.data,
-                                   cap, out_off.ctypes.data, ret.ctypes.data, C.byref(need))
-        if rc == -3 and need.value > cap:  # DG_E_NOMEM: the inserts outgrew the guess
-            cap = int(need.value)
-            continue
-        _lib.check(rc)
-        break
+        return L.dg_editm_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
+                                     vt.ctypes.data, None if val is None else val.ctypes.data,
+                                     None if val_off is None else val_off.ctypes.data, vl.ctypes.data, out.ctypes.data,
+                                     cap, out_off.ctypes.data, ret.ctypes.data, C.byref(need)), out
+
+    out = _until_fits(call, int(in_off[n]) + vtotal, need)  # a guess the inserts may outgrow
     return [EditManyResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes(), k) for i in range(n)]
 
 
@@ -843,13 +816,10 @@ def set_many_batch(msgs: Sequence[bytes], parent, items, desc=None, root_type: i
     items' steps are not looked at. Semantics: EditManyPlan."""
     plan = parent if isinstance(parent, EditManyPlan) else \
         EditManyPlan(parent, [it[0] for it in items], EDIT_SET, desc, ctx)
-    try:
+    with _unless_given(plan, parent):
         if plan.op != EDIT_SET or plan.k != len(items):
             raise ValueError("set_many_batch needs an EDIT_SET plan of as many steps as items")
         return _editm_batch(msgs, plan, [it[1] for it in items], [it[2] for it in items], root_type)
-    finally:
-        if plan is not parent:
-            plan.close()
 
 
 def unset_many_batch(msgs: Sequence[bytes], parent, steps=None, desc=None, root_type: int = STRUCT,
@@ -858,13 +828,10 @@ def unset_many_batch(msgs: Sequence[bytes], parent, steps=None, desc=None, root_
     EditManyPlan of op EDIT_UNSET) are dropped from every message, every step
     addressing the original message. Semantics: EditManyPlan."""
     plan = parent if isinstance(parent, EditManyPlan) else EditManyPlan(parent, steps, EDIT_UNSET, desc, ctx)
-    try:
+    with _unless_given(plan, parent):
         if plan.op != EDIT_UNSET:
             raise ValueError("unset_many_batch needs an EDIT_UNSET plan")
         return _editm_batch(msgs, plan, None, None, root_type)
-    finally:
-        if plan is not parent:
-            plan.close()
 
 
 def edit_many_device(plan: EditManyPlan, thrift, in_off, n: int, val_types, val, val_off, val_lens, out, out_off,
@@ -877,10 +844,7 @@ def edit_many_device(plan: EditManyPlan, thrift, in_off, n: int, val_types, val,
     None: val holds the K values back to back, val_lens[j] bytes each, for
     every message. ret int64[n]: status | existed mask << 8 | failing item
     << 16 | aux << 32. An UNSET plan ignores the value arguments."""
-    if stream is None and hasattr(thrift, "device"):
-        import torch
-        stream = torch.cuda.current_stream(thrift.device)
-    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    s = _stream_handle(stream, thrift)
     vt = np.asarray(val_types if val_types is not None else [0] * plan.k, dtype=np.uint8)
     vl = np.asarray(val_lens if val_lens is not None else [0] * plan.k, dtype=np.uint64)
     if len(vt) != plan.k or len(vl) != plan.k:
@@ -967,7 +931,7 @@ def children_records(msgs: Sequence[bytes], path=(), recurse: bool = False, desc
     recs[rec_off[i]:rec_off[i + 1]]. count_only stops after the count (recs is
     empty): head["direct"] is batched Node.Len."""
     ps = _one_path(path, desc, ctx)
-    try:
+    with _unless_given(ps, path):
         n = len(msgs)
         L = _lib.lib()
         head = np.zeros(n, dtype=KIDS_HEAD_DTYPE)
@@ -978,25 +942,17 @@ def children_records(msgs: Sequence[bytes], path=(), recurse: bool = False, desc
             _lib.check(L.dg_kids_batch_host(ps.ctx.h, ps.h, root_type, flags, None, None, 0, None, rec_off.ctypes.data, None,
                                             0, C.byref(need)))
             return head, rec_off, np.zeros(0, dtype=KIDS_REC_DTYPE)
-        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-        in_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens, out=in_off[1:])
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
-        cap = 0 if count_only else int(in_off[n]) // 8 + 64  # a guess; the call says what it needs
-        while True:
+        arena, in_off = _arena(msgs)
+
+        def call(cap):
             recs = np.zeros(cap, dtype=KIDS_REC_DTYPE)
-            rc = L.dg_kids_batch_host(ps.ctx.h, ps.h, root_type, flags, arena.ctypes.data, in_off.ctypes.data, n,
-                                      head.ctypes.data, rec_off.ctypes.data, recs.ctypes.data if cap else None, cap,
-                                      C.byref(need))
-            if rc == -3 and need.value > cap and not count_only:  # DG_E_NOMEM
-                cap = int(need.value)
-                continue
-            _lib.check(rc)
-            break
+            return L.dg_kids_batch_host(ps.ctx.h, ps.h, root_type, flags, arena.ctypes.data, in_off.ctypes.data, n,
+                                        head.ctypes.data, rec_off.ctypes.data, recs.ctypes.data if cap else None, cap,
+                                        C.byref(need)), recs
+
+        # a guess the call corrects; no records and no room: the call only counts
+        recs = _until_fits(call, 0 if count_only else int(in_off[n]) // 8 + 64, need)
         return head, rec_off, recs[:0 if count_only else int(rec_off[n])]
-    finally:
-        if ps is not path:
-            ps.close()
 
 
 def children_batch(msgs: Sequence[bytes], path=(), recurse: bool = False, desc=None, root_type: int = STRUCT,
@@ -1019,10 +975,7 @@ def children_device(pathset: PathSet, thrift, in_off, n: int, head, rec_off, rec
     with the same batch, path and mode. Asynchronous on `stream` (a torch
     stream, a raw stream handle, or None for torch's current stream when
     `thrift` is a tensor)."""
-    if stream is None and hasattr(thrift, "device"):
-        import torch
-        stream = torch.cuda.current_stream(thrift.device)
-    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    s = _stream_handle(stream, thrift)
     flags = (KIDS_F_RECURSE if recurse else 0) | (KIDS_F_COUNTED if counted else 0)
     _lib.check(_lib.lib().dg_kids_batch_device(pathset.ctx.h, pathset.h, root_type, flags, _ptr(thrift), _ptr(in_off), n,
                                                _ptr(head), _ptr(rec_off), _ptr(recs), rec_cap, s, max_len))

@@ -1,8 +1,8 @@
 """GPU: what the batch size and the stream, not the message, decide in the cut
 (batched MarshalTo) and the edit (batched SetByPath / UnsetByPath): the wave
 kernels' stride loops over a queue or a batch longer than their grid
-(cut_kern.hip, edit_kern.hip; the grids are set in cut_host.hip and
-edit_host.hip), launches of one context with no synchronisation between them on
+(cut_kern.hip, edit_kern.hip; the grids are set in cut_host.hip and, for
+edit_host.hip, in host_internal.h), launches of one context with no synchronisation between them on
 one stream and on several (the cut queue's two counters, the events that order
 the streams), the queue and the record scratch growing while the launch before
 may still use the old ones, and an edit interleaved with a GetByPath, whose
@@ -36,7 +36,7 @@ FILL, GUARD = 0xEE, 64
 F = R.FIELD
 # the wave kernels' grids: min(ceil(n / WAVES), factor * CU) blocks of WAVES waves
 CUT_GRID_FACTOR = 4   # cut_host.hip, cut_launch: `(uint64_t)c->n_cu * 4`
-EDIT_GRID_FACTOR = 8  # edit_host.hip, edit_launch: `(uint64_t)c->n_cu * 8`
+EDIT_GRID_FACTOR = 8  # host_internal.h, launch_splice_routes (edit_launch's): `(uint64_t)c->n_cu * 8`
 DISTINCT = 61
 
 
