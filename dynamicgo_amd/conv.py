@@ -22,6 +22,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._batch import arena as _arena, split as _split, until_fits as _until_fits
 from . import http as H
 from .thrift import FlatDescriptor, TypeDescriptor, flatten, TYPE_NAMES, ValueMappingError
 
@@ -364,10 +365,7 @@ class BinaryConv:
         if flags & (F_VALUE_MAPPING | F_HM_SPLIT):
             flags |= F_CB_COLLECT  # every callback of a pass at once (k callbacks: 2 passes)
         m = len(msgs)
-        lens = np.fromiter((len(x) for x in msgs), dtype=np.uint64, count=m)
-        in_off = np.zeros(m + 1, dtype=np.uint64)
-        np.cumsum(lens, out=in_off[1:])
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        arena, in_off = _arena(msgs)
         pool = bytearray(hm_bytes)
         cb = None
         keep = []
@@ -395,19 +393,16 @@ class BinaryConv:
             extra = len(pool) + 64 * m
         rets = np.zeros(max(m, 1), dtype=np.uint64)
         out_off = np.zeros(m + 1, dtype=np.uint64)
-        cap = int(lens.sum()) * 4 + 64 * m + 64 + extra
         need = C.c_uint64(0)
-        for _ in range(2):
+
+        def call(cap):
             out = np.zeros(cap, dtype=np.uint8)
-            rc = L.dg_j2t_batch_host_cb(ctx.h, ctx.desc(flat), flat.root_type, arena.ctypes.data, in_off.ctypes.data,
-                                        m, flags, C.byref(cb) if cb is not None else None, out.ctypes.data, cap,
-                                        out_off.ctypes.data, rets.ctypes.data, C.byref(need))
-            if rc == -3 and need.value > cap:  # DG_E_NOMEM: once more with the size it needs
-                cap = int(need.value) + 64
-                continue
-            break
-        _lib.check(rc)
-        return [out[int(out_off[k]):int(out_off[k + 1])].tobytes() for k in range(m)], rets[:m]
+            return L.dg_j2t_batch_host_cb(ctx.h, ctx.desc(flat), flat.root_type, arena.ctypes.data, in_off.ctypes.data,
+                                          m, flags, C.byref(cb) if cb is not None else None, out.ctypes.data, cap,
+                                          out_off.ctypes.data, rets.ctypes.data, C.byref(need)), out
+
+        out = _until_fits(call, int(in_off[m]) * 4 + 64 * m + 64 + extra, need)
+        return _split(out, out_off), rets[:m]
 
     def _serve_callbacks(self, flat: FlatDescriptor, msgs: Sequence[bytes], flags: int, outs, rets, errs,
                          hm_rows=None, n_hm: int = 0, hm_bytes: bytes = b"", hm_end=None):
@@ -639,35 +634,27 @@ class BinaryConv:
         flat = self._flat(desc)
         ctx = self._ctx()
         n = len(msgs)
-        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-        in_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens, out=in_off[1:])
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        arena, in_off = _arena(msgs)
         rets = np.zeros(max(n, 1), dtype=np.uint64)
         out_off = np.zeros(n + 1, dtype=np.uint64)
-        cap = int(lens.sum()) * 4 + 64 * n + 64 if out_cap is None else out_cap
-        out = np.zeros(max(cap, 1), dtype=np.uint8)
         need = C.c_uint64(0)
         L = _lib.lib()
         flags = to_flags(self.opts) | extra_flags
         if flags & F_VALUE_MAPPING:
             flags |= F_CB_COLLECT  # every value-mapping callback of a pass at once
 
-        def call(out, cap):
+        def call(cap):
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
             if chunks > 0:
                 return L.dg_j2t_pipeline_host(ctx.h, ctx.desc(flat), flat.root_type, arena.ctypes.data,
                                               in_off.ctypes.data, n, flags, chunks, out.ctypes.data, cap,
-                                              out_off.ctypes.data, rets.ctypes.data, C.byref(need))
+                                              out_off.ctypes.data, rets.ctypes.data, C.byref(need)), out
             return L.dg_j2t_batch_host(ctx.h, ctx.desc(flat), flat.root_type, arena.ctypes.data, in_off.ctypes.data,
                                        n, flags, out.ctypes.data, cap, out_off.ctypes.data,
-                                       rets.ctypes.data, C.byref(need))
-        rc = call(out, cap)
-        if rc == -3 and need.value > cap:
-            cap = int(need.value) + 64
-            out = np.zeros(cap, dtype=np.uint8)
-            rc = call(out, cap)
-        _lib.check(rc)
-        outs = [out[int(out_off[i]):int(out_off[i + 1])].tobytes() for i in range(n)]
+                                       rets.ctypes.data, C.byref(need)), out
+
+        out = _until_fits(call, int(in_off[n]) * 4 + 64 * n + 64 if out_cap is None else out_cap, need)
+        outs = _split(out, out_off)
         rets = rets[:n]
         vm_errs = {}
         if flags & F_VALUE_MAPPING and any((int(r) & 0xFF) in _CB_CODES for r in rets):
@@ -733,19 +720,16 @@ class Aggregator:
         """BinaryConv.Do through the aggregator (thread-safe; ctypes drops the
         GIL for the blocking call)."""
         L = _lib.lib()
-        cap = 4 * len(jbytes) + 64
-        for _ in range(2):
+        ol, ret = C.c_size_t(0), C.c_uint64(0)
+
+        def call(cap):
             out = C.create_string_buffer(max(cap, 1))
-            ol, ret = C.c_size_t(0), C.c_uint64(0)
-            rc = L.dg_agg_do(self.h, jbytes, len(jbytes), out, cap, C.byref(ol), C.byref(ret))
-            if rc == -3 and ol.value > cap:  # DG_E_NOMEM: retry with the size it needs
-                cap = ol.value
-                continue
-            _lib.check(rc)
-            if ret.value != 0:
-                raise J2TError(int(ret.value), explain_native_error(int(ret.value), jbytes))
-            return out.raw[:ol.value] or None
-        raise J2TError(0, "aggregator: output did not fit")
+            return L.dg_agg_do(self.h, jbytes, len(jbytes), out, cap, C.byref(ol), C.byref(ret)), out
+
+        out = _until_fits(call, 4 * len(jbytes) + 64, ol)  # DG_E_NOMEM leaves the size it needs in out_len
+        if ret.value != 0:
+            raise J2TError(int(ret.value), explain_native_error(int(ret.value), jbytes))
+        return out.raw[:ol.value] or None
 
     def drive(self, msgs: Sequence[bytes], threads: int = 16, window: int = 256):
         """The reference's b.RunParallel over Do (conv/j2t/conv_timing_test.go:
@@ -753,12 +737,9 @@ class Aggregator:
         flight (dg_agg_drive). Returns (outputs, statuses, latency ns per
         message, wall seconds); statuses are the packed status words."""
         n = len(msgs)
-        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-        in_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens, out=in_off[1:])
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        arena, in_off = _arena(msgs)
         out_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens * 4 + 4096, out=out_off[1:])
+        np.cumsum(np.diff(in_off) * 4 + 4096, out=out_off[1:])
         out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
         out_len = np.zeros(max(n, 1), dtype=np.uint64)
         rets = np.zeros(max(n, 1), dtype=np.uint64)
@@ -783,12 +764,9 @@ class Aggregator:
         message, wall seconds, stats [parks, retries, wake-ups, callers, worker ns in
         wait, in submit, idle, in all])."""
         n = len(msgs)
-        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-        in_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens, out=in_off[1:])
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        arena, in_off = _arena(msgs)
         out_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens * 4 + 4096, out=out_off[1:])
+        np.cumsum(np.diff(in_off) * 4 + 4096, out=out_off[1:])
         out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
         out_len = np.zeros(max(n, 1), dtype=np.uint64)
         rets = np.zeros(max(n, 1), dtype=np.uint64)
@@ -893,14 +871,13 @@ class HTTPConv:
         flat = cv._flat(self.st)
         bodies = [r.get_body() for r in reqs]
         n = len(bodies)
-        lens = np.fromiter((len(b) for b in bodies), dtype=np.int64, count=n)
-        in_off = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(lens, out=in_off[1:])
+        arena, in_off = _arena(bodies)
+        in_off = in_off.view(np.int64)
         slots = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum((lens * 4 + 64 + 7) & ~7, out=slots[1:])
+        np.cumsum((np.diff(in_off) * 4 + 64 + 7) & ~7, out=slots[1:])
         dev = torch.device("cuda", ctx.device)
         st = torch.cuda.current_stream(dev)
-        d_json = torch.from_numpy(np.frombuffer(b"".join(bodies) + b"\0" * 64, dtype=np.uint8).copy()).to(dev)
+        d_json = torch.from_numpy(arena.copy()).to(dev)
         d_in = torch.from_numpy(in_off).to(dev)
         d_oo = torch.from_numpy(slots).to(dev)
         d_out = torch.empty(int(slots[-1]) + 64, dtype=torch.uint8, device=dev)

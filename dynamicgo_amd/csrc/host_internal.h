@@ -3,7 +3,7 @@
  * GPU resources (device and pinned arrays, events, streams), the rule that
  * orders a shared buffer across streams, the context, descriptor and
  * per-stream scratch records, the entry guard, the argument records of one
- * batch, the host batch of the thrift/generic entries (HostBatch) and the
+ * batch, the host batch of the thrift/generic and t2j entries (HostBatch) and the
  * error helpers (j2t_host.hip defines the functions; t2j_host,
  * tget_host, cut_host, edit_host, editm_host, kids_host and j2t_pipe use them).
  */
@@ -506,7 +506,8 @@ inline int empty_batch(uint64_t *off, uint64_t *need)
     return DG_OK;
 }
 
-/* One batch of a thrift/generic host entry (tget, cut, edit, editm, kids), made
+/* One batch of a host entry (tget, cut, edit, editm, kids, t2j; j2t's overflow
+ * rerun takes copy / sync and the destructor only), made
  * after Entry: the layout (host_layout.h) in vectors it owns, their upload into
  * the context's staging buffers, the packing and the download. Every copy is
  * asynchronous on s and several read io / so / vo, so the destructor
@@ -579,12 +580,14 @@ struct HostBatch {
         HIPCHK(hipMemsetAsync(c->d_json + io[n], 0, 64, s));
         return copy(c->d_in_off, io.data(), (n + 1) * 8, hipMemcpyHostToDevice);
     }
-    /* the output side: the slots, their lengths and status words, the packing */
-    int upload_slots()
+    /* the output side: the slots, their lengths and status words, and for an
+     * entry that packs on the device (all but t2j) the packing */
+    int upload_slots(bool packs = true)
     {
         int rc;
         if ((rc = c->d_out.grow(so[n] + 64)) || (rc = c->d_out_off.grow(n + 1)) || (rc = c->d_out_len.grow(n + 1)) ||
-            (rc = c->d_ret.grow(n + 1)) || (rc = c->d_pack.grow(so[n] + 64)) || (rc = c->d_pack_off.grow(n + 1)))
+            (rc = c->d_ret.grow(n + 1)) ||
+            (packs && ((rc = c->d_pack.grow(so[n] + 64)) || (rc = c->d_pack_off.grow(n + 1)))))
             return rc;
         return copy(c->d_out_off, so.data(), (n + 1) * 8, hipMemcpyHostToDevice);
     }

@@ -1,6 +1,6 @@
 /*
  * host_layout.h — the arithmetic of one host batch, shared by the host entries
- * of tget, cut, edit, editm and kids (HostBatch, host_internal.h): offsets
+ * of tget, cut, edit, editm, kids and t2j (HostBatch, host_internal.h): offsets
  * rebased to 0, 16-byte slots, the gather of a rerun, value offsets. Plain
  * C++17 and no HIP type, so a CPU program can include it
  * (tests/host_layout_host.cpp). Every array is the caller's, of exactly the

@@ -798,6 +798,9 @@ static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const BatchArg
         for (uint64_t i : redo) rb += ioff[i + 1] - ioff[i];
         const uint64_t rhw = hm ? 2 * m * nhm + m * nvm + hmb / 8 : 0;
         std::vector<uint8_t> up(16 * (m + 1) + 8 * rhw + rb + 64, 0);
+        /* the rerun's asynchronous copies read up and write rdown, both declared before hb: its destructor
+         * waits for them wherever the rerun returns */
+        HostBatch hb(c, s);
         uint64_t *io = (uint64_t *)(void *)up.data(), *so = io + m + 1, *rhm = so + m + 1;
         uint8_t *rj = (uint8_t *)(void *)(rhm + rhw);
         io[0] = so[0] = 0;
@@ -820,7 +823,7 @@ static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const BatchArg
         const uint64_t *r_in = (const uint64_t *)(void *)c->d_json, *r_oo = r_in + m + 1;
         uint64_t *r_ret = (uint64_t *)(void *)c->d_pack; /* rhead <= head: d_pack is large enough */
         uint32_t *r_ol = (uint32_t *)(void *)(c->d_pack + 8 * m);
-        HIPCHK(hipMemcpyAsync(c->d_json, up.data(), up.size(), hipMemcpyHostToDevice, s));
+        if ((rc = hb.copy(c->d_json, up.data(), up.size(), hipMemcpyHostToDevice))) return rc;
         if (hm)
             b.hm = HMIn{nhm ? (const dg_hm_entry *)(const void *)(r_oo + m + 1) : nullptr, (uint32_t)nhm,
                         (const uint8_t *)(const void *)(r_oo + m + 1 + 2 * m * nhm + m * nvm),
@@ -829,9 +832,9 @@ static int batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const BatchArg
         b.out = c->d_out, b.out_off = r_oo, b.out_len = r_ol, b.ret = r_ret;
         if ((rc = launch(c, d, root, b, s))) return rc;
         rdown.resize(rhead + so[m]);
-        HIPCHK(hipMemcpyAsync(rdown.data(), c->d_pack, rhead, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(rdown.data() + rhead, c->d_out, so[m], hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        if ((rc = hb.copy(rdown.data(), c->d_pack, rhead, hipMemcpyDeviceToHost)) ||
+            (rc = hb.copy(rdown.data() + rhead, c->d_out, so[m], hipMemcpyDeviceToHost)) || (rc = hb.sync()))
+            return rc;
         redo_so.assign(so, so + m + 1);
         for (uint64_t k = 0; k < m; k++) {
             const uint64_t i = redo[k];

@@ -245,74 +245,55 @@ static int t2j_batch_host(dg_ctx *c, const dg_desc *d, uint32_t root, const Batc
             return set_err(DG_E_INVALID, "callback answers of message %llu outside the bytes", (unsigned long long)i);
     Entry g(c, true);
     if (g.rc) return g.rc;
-    const uint64_t base = in_off[0];
-    std::vector<uint32_t> olen(n);
+    if (n == 0) return empty_batch(out_off, o.out_need);
+    /* what a copy reads or writes is declared before the batch, whose destructor waits for the copies */
+    std::vector<uint64_t> todo, slot_of(n, 0), r, ax; /* slot_of: stage offset of message i's final bytes */
+    std::vector<uint32_t> olen(n, 0), l;
     std::vector<uint8_t> stage;
-    const hipStream_t s = g.s;
+    std::vector<dg_cb_entry> e; /* the rerun's answer entries */
+    HostBatch hb(c, g.s);
     int rc;
     /* pass 0: every message in a dg_t2j_slot_bound slot; pass 1: the
-     * overflowed ones again, each in a slot of exactly the size it reported */
-    std::vector<uint64_t> todo(n);
-    for (uint64_t i = 0; i < n; i++) todo[i] = i;
-    std::vector<uint64_t> slot_of(n, 0); /* stage offset of message i's final bytes */
-    uint64_t max_len = 0;
-    for (uint64_t i = 0; i < n; i++) max_len = std::max<uint64_t>(max_len, in_off[i + 1] - in_off[i]);
-    for (int pass = 0; pass < 2 && !todo.empty(); pass++) {
-        const uint64_t m = todo.size();
-        std::vector<uint64_t> io(m + 1), so(m + 1);
-        io[0] = so[0] = 0;
-        for (uint64_t k = 0; k < m; k++) {
-            const uint64_t i = todo[k], len = in_off[i + 1] - in_off[i];
-            io[k + 1] = io[k] + len;
-            so[k + 1] = so[k] + (pass == 0 ? dg_t2j_slot_bound(len) : ((uint64_t)olen[i] + 64 + 7) & ~7ull);
-        }
-        if ((rc = c->d_json.grow(io[m] + 64))) return rc;
-        if ((rc = c->d_in_off.grow(m + 1))) return rc;
-        if ((rc = c->d_out.grow(so[m] + 64))) return rc;
-        if ((rc = c->d_out_off.grow(m + 1))) return rc;
-        if ((rc = c->d_out_len.grow(m + 1))) return rc;
-        if ((rc = c->d_ret.grow(m + 1))) return rc;
-        if (aux && (rc = c->d_aux.grow(m + 1))) return rc;
-        if (ans) { /* [m entries | the answer bytes] */
-            if ((rc = c->d_cb.grow(8 * m + cb->len + 8))) return rc;
-            std::vector<dg_cb_entry> e(m);
-            for (uint64_t k = 0; k < m; k++) e[k] = ans[todo[k]];
-            HIPCHK(hipMemcpyAsync(c->d_cb, e.data(), 8 * m, hipMemcpyHostToDevice, s));
-            if (cb->len) HIPCHK(hipMemcpyAsync(c->d_cb + 8 * m, cb->bytes, cb->len, hipMemcpyHostToDevice, s));
-            HIPCHK(hipStreamSynchronize(s)); /* e is a local */
-        }
-        if (pass == 0) {
-            HIPCHK(hipMemcpyAsync(c->d_json, thrift + base, io[m], hipMemcpyHostToDevice, s));
-        } else {
-            for (uint64_t k = 0; k < m; k++)
-                HIPCHK(hipMemcpyAsync(c->d_json + io[k], thrift + in_off[todo[k]], io[k + 1] - io[k],
-                                      hipMemcpyHostToDevice, s));
-        }
-        HIPCHK(hipMemsetAsync(c->d_json + io[m], 0, 64, s));
-        HIPCHK(hipMemcpyAsync(c->d_in_off, io.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(c->d_out_off, so.data(), (m + 1) * 8, hipMemcpyHostToDevice, s));
+     * overflowed ones again, each in a slot of the size it reported + 64.
+     * Each pass downloads its whole slot arena: which statuses keep their bytes
+     * is t2j's own rule, and an overflowed message's length is what it needs. */
+    for (int pass = 0; pass < 2 && (pass == 0 || !todo.empty()); pass++) {
+        const uint64_t m = pass ? todo.size() : n;
+        r.resize(m), l.resize(m), ax.resize(aux ? m : 0);
+        if ((rc = hb.layout(in_off, pass ? todo.data() : nullptr, m, [&](uint64_t i, uint64_t len) -> uint64_t {
+                return pass == 0 ? dg_t2j_slot_bound(len) : (uint64_t)olen[i] + 64;
+            })) ||
+            (rc = hb.upload_messages(thrift, in_off)) || (rc = hb.upload_slots(false)) ||
+            (aux && (rc = c->d_aux.grow(m + 1))))
+            return rc;
         BatchArgs b;
-        b.src = c->d_json, b.in_off = c->d_in_off, b.n = m, b.flags = opts, b.max_len = max_len;
+        b.src = c->d_json, b.in_off = c->d_in_off, b.n = m, b.flags = opts, b.max_len = hb.max_len;
         b.out = c->d_out, b.out_off = c->d_out_off, b.out_len = c->d_out_len, b.ret = c->d_ret;
         if (aux) b.aux = c->d_aux;
-        if (ans) b.hm.vm = (const dg_cb_entry *)(const void *)(uint8_t *)c->d_cb, b.hm.bytes = c->d_cb + 8 * m;
-        if ((rc = t2j_launch(c, d, root, b, s))) return rc;
-        std::vector<uint64_t> r(m), ax(aux ? m : 0);
-        std::vector<uint32_t> l(m);
-        if (aux) HIPCHK(hipMemcpyAsync(ax.data(), c->d_aux, m * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(r.data(), c->d_ret, m * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(l.data(), c->d_out_len, m * 4, hipMemcpyDeviceToHost, s));
-        const uint64_t off0 = stage.size();
-        stage.resize(off0 + so[m]);
-        HIPCHK(hipMemcpyAsync(stage.data() + off0, c->d_out, so[m], hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        if (ans) { /* [m entries | the answer bytes]; the rerun's entries gathered */
+            e.resize(pass ? m : 0);
+            for (uint64_t k = 0; k < e.size(); k++) e[k] = ans[todo[k]];
+            if ((rc = c->d_cb.grow(8 * m + cb->len + 8)) ||
+                (rc = hb.copy(c->d_cb, pass ? e.data() : ans, 8 * m, hipMemcpyHostToDevice)) ||
+                (rc = hb.copy(c->d_cb + 8 * m, cb->bytes, cb->len, hipMemcpyHostToDevice)))
+                return rc;
+            b.hm.vm = (const dg_cb_entry *)(const void *)(uint8_t *)c->d_cb, b.hm.bytes = c->d_cb + 8 * m;
+        }
+        if ((rc = t2j_launch(c, d, root, b, g.s))) return rc;
+        const uint64_t off0 = stage.size(), slots = hb.so[m];
+        stage.resize(off0 + slots);
+        if ((rc = hb.copy(ax.data(), c->d_aux, ax.size() * 8, hipMemcpyDeviceToHost)) ||
+            (rc = hb.copy(r.data(), c->d_ret, m * 8, hipMemcpyDeviceToHost)) ||
+            (rc = hb.copy(l.data(), c->d_out_len, m * 4, hipMemcpyDeviceToHost)) ||
+            (rc = hb.copy(stage.data() + off0, c->d_out, slots, hipMemcpyDeviceToHost)) || (rc = hb.sync()))
+            return rc;
         std::vector<uint64_t> next;
         for (uint64_t k = 0; k < m; k++) {
-            const uint64_t i = todo[k];
+            const uint64_t i = pass ? todo[k] : k;
             ret[i] = r[k];
             olen[i] = l[k];
             if (aux) aux[i] = ax[k];
-            slot_of[i] = off0 + so[k];
+            slot_of[i] = off0 + hb.so[k];
             if ((uint8_t)r[k] == DG_ST_OUT_OVERFLOW) {
                 if (pass == 1)
                     return set_err(DG_E_NOMEM, "message %llu overflowed its exact-size slot", (unsigned long long)i);

@@ -27,6 +27,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from ._batch import arena as _arena, split as _split, until_fits as _until_fits
 from .conv import Context, default_context
 from .http import ConvError
 
@@ -173,27 +174,6 @@ def _unless_given(made, given):
     finally:
         if made is not given:
             made.close()
-
-
-def _arena(msgs):
-    """(arena, in_off) of a non-empty batch: the messages back to back with 16
-    spare bytes, and uint64[n + 1] offsets from 0."""
-    n = len(msgs)
-    in_off = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum(np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n), out=in_off[1:])
-    return np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8), in_off
-
-
-def _until_fits(call, cap: int, need):
-    """call(cap) -> (rc, out) with room for `cap`; on DG_E_NOMEM (-3) with a
-    larger *need, once more at that size. Returns the out that fitted."""
-    while True:
-        rc, out = call(cap)
-        if rc == -3 and need.value > cap:
-            cap = int(need.value)
-            continue
-        _lib.check(rc)
-        return out
 
 
 class PathSet(_Handle):
@@ -510,7 +490,7 @@ def marshal_to_batch(msgs: Sequence[bytes], from_desc, to_desc=None, opts=None,
                                        out.ctypes.data, cap, out_off.ctypes.data, ret.ctypes.data, C.byref(need)), out
 
         out = _until_fits(call, int(in_off[n]) + 4096, need)  # a guess the literals may outgrow
-        return [CutResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes()) for i in range(n)]
+        return [CutResult(r, o) for r, o in zip(ret.tolist(), _split(out, out_off))]
 
 
 def marshal_to_device(plan: CutPlan, thrift, in_off, n: int, out, out_off, out_len, ret, opts=None, stream=None,
@@ -641,7 +621,7 @@ def _edit_batch(msgs, plan: EditPlan, values, val_type: int, root_type: int) -> 
                                     out_off.ctypes.data, ret.ctypes.data, C.byref(need)), out
 
     out = _until_fits(call, int(in_off[n]) + vtotal, need)  # a guess the inserts may outgrow
-    return [EditResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes()) for i in range(n)]
+    return [EditResult(r, o) for r, o in zip(ret.tolist(), _split(out, out_off))]
 
 
 def set_by_path_batch(msgs: Sequence[bytes], path, values, val_type: int, desc=None, root_type: int = STRUCT,
@@ -802,7 +782,7 @@ def _editm_batch(msgs, plan: EditManyPlan, values, val_types, root_type: int) ->
                                      cap, out_off.ctypes.data, ret.ctypes.data, C.byref(need)), out
 
     out = _until_fits(call, int(in_off[n]) + vtotal, need)  # a guess the inserts may outgrow
-    return [EditManyResult(int(ret[i]), out[int(out_off[i]):int(out_off[i + 1])].tobytes(), k) for i in range(n)]
+    return [EditManyResult(r, o, k) for r, o in zip(ret.tolist(), _split(out, out_off))]
 
 
 def set_many_batch(msgs: Sequence[bytes], parent, items, desc=None, root_type: int = STRUCT,

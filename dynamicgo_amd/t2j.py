@@ -33,6 +33,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._batch import arena as _arena, split as _split, until_fits as _until_fits
 from . import http as H
 from . import thrift as T
 from .conv import Context, Options, default_context
@@ -696,14 +697,9 @@ class BinaryConv:
         flat = self._flat(desc)
         ctx = self._ctx()
         n = len(msgs)
-        lens = np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n)
-        in_off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(lens, out=in_off[1:])
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, dtype=np.uint8)
+        arena, in_off = _arena(msgs)
         rets = np.zeros(max(n, 1), dtype=np.uint64)
         out_off = np.zeros(n + 1, dtype=np.uint64)
-        cap = int(lens.sum()) * 3 + 64 * n + 64
-        out = np.zeros(cap, dtype=np.uint8)
         need = C.c_uint64(0)
         L = _lib.lib()
         d = ctx.desc_t2j(flat)
@@ -717,19 +713,16 @@ class BinaryConv:
                 blob += a
             ab = np.frombuffer(bytes(blob) + b"\0" * 8, dtype=np.uint8)
             cb = _lib.CBTables(None, 0, C.cast(tab, C.c_void_p), ab.ctypes.data, len(blob))
-        for _ in range(2):
-            rc = L.dg_t2j_batch_host_cb(ctx.h, d, flat.root_type, arena.ctypes.data, in_off.ctypes.data, n, opts,
-                                        out.ctypes.data, cap, out_off.ctypes.data, rets.ctypes.data,
-                                        C.byref(need), aux.ctypes.data if aux is not None else None,
-                                        C.byref(cb) if cb is not None else None)
-            if rc == -3 and need.value > cap:
-                cap = int(need.value) + 64
-                out = np.zeros(cap, dtype=np.uint8)
-                continue
-            break
-        _lib.check(rc)
-        outs = [out[int(out_off[i]):int(out_off[i + 1])].tobytes() for i in range(n)]
-        return outs, rets[:n], aux
+
+        def call(cap):
+            out = np.zeros(cap, dtype=np.uint8)
+            return L.dg_t2j_batch_host_cb(ctx.h, d, flat.root_type, arena.ctypes.data, in_off.ctypes.data, n, opts,
+                                          out.ctypes.data, cap, out_off.ctypes.data, rets.ctypes.data,
+                                          C.byref(need), aux.ctypes.data if aux is not None else None,
+                                          C.byref(cb) if cb is not None else None), out
+
+        out = _until_fits(call, int(in_off[n]) * 3 + 64 * n + 64, need)
+        return _split(out, out_off), rets[:n], aux
 
     def do_device(self, desc, thrift, in_off, out, out_off, out_len, ret, stream=None):
         """Device-resident batch over torch tensors: thrift uint8[>= in_off[-1]

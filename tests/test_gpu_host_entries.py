@@ -1,13 +1,20 @@
 """GPU: the five thrift/generic host entries (dg_tget / dg_cut / dg_edit /
-dg_editm / dg_kids _batch_host) through ctypes with an arena that does not
+dg_editm / dg_kids _batch_host) and the two conversion entries (dg_t2j /
+dg_j2t _batch_host) through ctypes with an arena that does not
 start at 0. The Python wrappers always pass in_off[0] = 0, so the rebasing the
-entries share (csrc/host_layout.h, HostBatch) is reached only here: every
+entries share (csrc/host_layout.h, HostBatch; j2t's own in batch_host) is
+reached only here: every
 entry is called once with the messages at base 0 and once with the same
 messages behind 37 bytes of 0xEE (edit and editm: per-message values behind 11
-bytes); the two answers are byte-identical and the first equals the checker's.
-cut, edit and editm also answer a one-byte-short output with DG_E_NOMEM and
-the size to retry with."""
+bytes); the two answers are byte-identical and the first equals the checker's
+(t2j: JSON written by hand).
+cut, edit, editm, t2j and j2t also answer a one-byte-short output with
+DG_E_NOMEM and the size to retry with. The t2j and j2t batches each hold
+messages that outgrow their first slot, so the rerun pass gathers them from
+behind the padding. dg_t2j_batch_host refuses descending offsets and writes
+nothing."""
 import ctypes as C
+import struct
 
 import numpy as np
 import pytest
@@ -172,3 +179,74 @@ def test_editm():
                                                            vl.ctypes.data, *o), n, total)
 
         same_packed(twice(run), want, "host entry")
+
+
+def test_t2j():
+    from dynamicgo_amd import conv, thrift as T
+    L, _ = lib()
+    fl = T.flatten(T.struct_type("S", [T.FieldDescriptor(1, "s", T.builtin("string"), T.OPTIONAL)]))
+    ks = (0, 1, 7, 100)
+    msgs = [b"\x0b\x00\x01" + struct.pack(">i", k) + b"\x01" * k + b"\x00" for k in ks] + [b"\x00"]
+    want = [(0, b'{"s":"' + b"\\u0001" * k + b'"}') for k in ks] + [(0, b"{}")]
+    n, total = len(msgs), sum(len(o) for _, o in want)
+    # k = 100 alone (108 bytes in, 608 out, a first slot of 512) takes the rerun pass: todo = [3]
+    assert (len(msgs[3]), len(want[3][1]), L.dg_t2j_slot_bound(108)) == (108, 608, 512)
+    assert [len(o) > L.dg_t2j_slot_bound(len(m)) for m, (_, o) in zip(msgs, want)] == [False, False, False, True, False]
+    ctx = conv.default_context()
+    d = ctx.desc_t2j(fl)
+
+    def run(pad):
+        a, off = arena(msgs, pad)
+        return packed(lambda *o: L.dg_t2j_batch_host(ctx.h, d, fl.root_type, a.ctypes.data, off.ctypes.data, n, 0, *o),
+                      n, total)
+
+    same_packed(twice(run), want, "host entry")
+
+
+def test_t2j_refuses_descending_offsets():
+    from dynamicgo_amd import conv, thrift as T
+    L, _ = lib()
+    fl = T.flatten(T.struct_type("S", [T.FieldDescriptor(1, "s", T.builtin("string"), T.OPTIONAL)]))
+    ctx = conv.default_context()
+    a = np.frombuffer(b"\x00" * 3 + b"\0" * 16, dtype=np.uint8)
+    off = np.array([0, 2, 1, 3], dtype=np.uint64)  # message 1 ends before it starts
+    out, out_off = np.full(64, 0xAB, dtype=np.uint8), np.full(4, 0xAB, dtype=np.uint64)
+    ret, need = np.full(3, 0xAB, dtype=np.uint64), C.c_uint64(0xAB)
+    rc = L.dg_t2j_batch_host(ctx.h, ctx.desc_t2j(fl), fl.root_type, a.ctypes.data, off.ctypes.data, 3, 0, out.ctypes.data,
+                             64, out_off.ctypes.data, ret.ctypes.data, C.byref(need))
+    assert rc == -1  # DG_E_INVALID
+    assert need.value == 0xAB and all((x == 0xAB).all() for x in (out, out_off, ret))
+
+
+def test_j2t():
+    import oracle
+    from dynamicgo_amd import conv, thrift as T
+    L, _ = lib()
+    fl = T.flatten(T.struct_type("Wide", [T.FieldDescriptor(i, "f%d" % i, T.builtin("i64"), T.DEFAULT)
+                                          for i in range(1, 13)]))
+    flags = 0x3  # allow unknown fields, write the default ones: every struct comes out as 12 fields, 133 bytes
+    full = b"{" + b",".join(b'"f%d":%d' % (i, -i) for i in range(1, 13)) + b"}"
+    msgs = [b"{}", full, b"[]", b'{"f3":-1}', b""]
+    chk = oracle.RefOracle() or oracle.PortOracle()
+    want = [chk.j2t(fl, m, flags) for m in msgs]
+
+    def field(i, v):
+        return b"\x0a" + struct.pack(">hq", i, v)
+
+    # by hand: the fields given in the order given, then the unset ones by id
+    assert want[0] == (0, b"".join(field(i, 0) for i in range(1, 13)) + b"\x00")
+    assert want[1] == (0, b"".join(field(i, -i) for i in range(1, 13)) + b"\x00")
+    assert want[3] == (0, field(3, -1) + b"".join(field(i, 0) for i in range(1, 13) if i != 3) + b"\x00")
+    assert want[2][0] != 0 and want[2][1] == b""
+    # 133 bytes outgrow dg_slot_bound of the two short structs: the rerun pass takes messages 0 and 3
+    assert [r == 0 and len(o) > L.dg_slot_bound(len(m)) for m, (r, o) in zip(msgs, want)] == [True, False, False, True, False]
+    n, total = len(msgs), sum(len(o) for _, o in want)
+    ctx = conv.default_context()
+    d = ctx.desc(fl)
+
+    def run(pad):
+        a, off = arena(msgs, pad)
+        return packed(lambda *o: L.dg_j2t_batch_host(ctx.h, d, fl.root_type, a.ctypes.data, off.ctypes.data, n, flags, *o),
+                      n, total)
+
+    same_packed(twice(run), want, "host entry")

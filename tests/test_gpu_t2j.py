@@ -639,6 +639,29 @@ def gpu_t2j_ans(flat, msgs, opts, answers):
     return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(n)], rets[:n]
 
 
+def test_answers_follow_a_message_into_the_rerun(chk):
+    """Three messages, the middle one with an answer and a JSON that outgrows
+    its first slot (100 control bytes -> 600): the rerun pass is that message
+    alone, so its answers are entry 1 of the table, gathered to entry 0."""
+    td = T.struct_type("R", [T.FieldDescriptor(1, "h", T.builtin("string"), http_mappings=[("api.header", "h")]),
+                             T.FieldDescriptor(2, "s", T.builtin("string"), T.OPTIONAL)])
+    fl = T.flatten(td)
+    side = T.flatten_t2j(fl)
+
+    def msg(h, s):
+        f = lambda i, v: b"" if v is None else b"\x0b" + struct.pack(">hi", i, len(v)) + v
+        return f(1, h) + f(2, s) + b"\x00"
+
+    msgs = [msg(None, b"plain"), msg(b"x", b"\x01" * 100), msg(b"y", b"z")]
+    answers = [b"", b"\x01", b"\x00"]  # none; write the mapped field as well; taken
+    want = [chk.t2j3(fl, side, m, HM, a)[:2] for m, a in zip(msgs, answers)]
+    assert [r for r, _ in want] == [0, 0, 0]  # with ans[0] (no answer) in its place the middle one would stop at its callback
+    assert chk.t2j3(fl, side, msgs[1], HM, b"")[0] & 0xFF == 12
+    assert len(want[1][1]) > _lib.lib().dg_t2j_slot_bound(len(msgs[1]))
+    outs, rets = gpu_t2j_ans(fl, msgs, HM, answers)
+    assert [(int(r), o) for r, o in zip(rets, outs)] == want
+
+
 def hm_desc():
     """Mapped fields at the root, in a root field's struct (resp passed on),
     in list / map elements (nil resp), inside a mapped container (its JSON
