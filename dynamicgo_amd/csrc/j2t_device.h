@@ -38,7 +38,7 @@ namespace dg {
 enum : uint32_t {
     E_EOF = 1, E_INVAL = 2, E_ESCAPE = 3, E_UNICODE = 4, E_NUMBER_FMT = 6, E_RECURSE_MAX = 7,
     E_FLOAT_INF = 8, E_DISMATCH_TYPE = 9, E_NULL_REQUIRED = 10, E_UNSUPPORT_THRIFT_TYPE = 11,
-    E_UNKNOWN_FIELD = 12, E_DISMATCH_TYPE2 = 13, E_DECODE_BASE64 = 14, E_HM = 19,
+    E_UNKNOWN_FIELD = 12, E_DISMATCH_TYPE2 = 13, E_DECODE_BASE64 = 14, E_OOM_KEY = 18, E_HM = 19,
     E_UNSUPPORT_VM_TYPE = 20, E_HM_END = 21, E_VM_END = 24
 };
 enum : int64_t { V_DOUBLE = 8, V_INTEGER = 9 };

@@ -496,7 +496,13 @@ struct Machine {
             BufSink sink{ws.keybuf, (int64_t)ws.keycap, false};
             int64_t l = unquote(src, s0, k.n, sink);
             if (l < 0) return pack((uint32_t)-l, (uint64_t)s0, (uint64_t)p);
-            if (sink.over) return pack0(DG_ST_DEEP, 0);
+            if (sink.over) {
+                /* the lane's buffer: the deep pass has a larger one. The deep pass's own: the reference
+                 * would grow its key cache (ERR_OOM_KEY, native/thrift.c:482-485, served by Go); here
+                 * that code is the message's status, value = the key's JSON bytes beyond the buffer */
+                if (ws.keycap >= (uint32_t)DEEP_KEYCAP) return pack0(E_OOM_KEY, (uint64_t)(k.n - (int64_t)ws.keycap));
+                return pack0(DG_ST_DEEP, 0);
+            }
             k.inbuf = true;
             k.n = l;
         }
