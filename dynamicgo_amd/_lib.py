@@ -27,7 +27,9 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_edit_create", "dg_edit_destroy", "dg_edit_slot_bound", "dg_edit_batch_device", "dg_edit_batch_host",
            "dg_editm_create", "dg_editm_destroy", "dg_editm_items", "dg_editm_slot_bound", "dg_editm_batch_device",
            "dg_editm_batch_host",
-           "dg_kids_batch_device", "dg_kids_batch_host"]
+           "dg_kids_batch_device", "dg_kids_batch_host",
+           "dg_cols_create", "dg_cols_destroy", "dg_cols_count", "dg_cols_batch_device", "dg_cols_list_device",
+           "dg_cols_batch_host"]
 
 _lib = None
 
@@ -131,6 +133,12 @@ def lib() -> C.CDLL:
         "dg_editm_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, P64]),
         "dg_kids_batch_device": (i32, [vp, vp, C.c_uint8, u32, vp, vp, u64, vp, vp, vp, u64, vp, u64]),
         "dg_kids_batch_host": (i32, [vp, vp, C.c_uint8, u32, vp, vp, u64, vp, vp, vp, u64, P64]),
+        "dg_cols_create": (i32, [vp, C.c_char_p, sz, C.c_char_p, u32, C.POINTER(vp)]),
+        "dg_cols_destroy": (None, [vp]),
+        "dg_cols_count": (u32, [vp]),
+        "dg_cols_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, u64]),
+        "dg_cols_list_device": (i32, [vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
+        "dg_cols_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, u64, P64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -5,7 +5,8 @@
  * per-stream scratch records, the entry guard, the argument records of one
  * batch, the host batch of the thrift/generic and t2j entries (HostBatch) and the
  * error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host, edit_host, editm_host, kids_host and j2t_pipe use them).
+ * tget_host, cut_host, edit_host, editm_host, kids_host, cols_host and j2t_pipe
+ * use them).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -277,6 +278,7 @@ struct Knobs {
     int64_t edit_wave_min = 4096; /* edit: outputs at least this long take the splice's wave route (0: all of them); ~1.1 KB x 65 536 at 4 lanes, 256 / 1024 / 4096 / 16384 -> 556 / 502 / 884 / 882 GB/s; ~83 KB x 4 096: lane route 203, wave route 1 407 */
     int64_t kids_wide_min = 256;  /* kids: a list, set or map node of fixed-size entries with at least this many children is emitted by the record-parallel kernel (0: never); emit pass, 16 384 x list<i64> of 64 / 128 / 256 / 1024, lane route 0.107 / 0.159 / 0.261 / 1.314 ms, wide route 0.264 / 0.270 / 0.278 / 0.350 */
     int64_t kids_no_scan = 0;     /* kids, timing only: 1 = a call leaves the scan out (rec_off is not written) */
+    int64_t cols_full_search = 0; /* cols, timing only: 1 = every lane of the list emit searches all n offsets (0: between the answers of its block's first and last lane) */
 };
 
 /* one chunk in flight of dg_j2t_pipeline_host (j2t_pipe.hip) */
@@ -336,6 +338,14 @@ struct dg_ctx {
     DevArr<uint32_t> kids_list, kids_cnt_buf;
     AltCounters kids_cnt;
     DevArr<uint64_t> kids_sums;
+    /* cols (cols_host.hip): the cell pass's deep frames (32 MB, allocated by
+     * the first call), its queue and two alternating queue counters, and the
+     * list scan's tile sums: its own, so that a lookup on another stream shares
+     * nothing with it */
+    SharedWs cols;
+    DevArr<uint32_t> cols_list, cols_cnt_buf;
+    AltCounters cols_cnt;
+    DevArr<uint64_t> cols_sums;
     /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB) */
     SharedWs t2j_tok;
     /* t2j deep pass: T2J_DEEP_DEPTH frames per lane (about 100 MB, allocated
@@ -408,6 +418,14 @@ struct dg_path {
     dg_ctx *ctx;
     DevArr<uint8_t> d_blob;
     dg_path_hdr hdr;
+};
+
+/* a column plan on its context's device (cols_host.hip): a path set and one kind per path */
+struct dg_cols {
+    dg_ctx *ctx;
+    DevArr<uint8_t> d_blob;
+    dg_path_hdr hdr;
+    uint8_t kinds[DG_TGET_MAX_PATHS];
 };
 
 /* one batch of messages (device pointers) and where the lookup's records go */
@@ -506,7 +524,7 @@ inline int empty_batch(uint64_t *off, uint64_t *need)
     return DG_OK;
 }
 
-/* One batch of a host entry (tget, cut, edit, editm, kids, t2j; j2t's overflow
+/* One batch of a host entry (tget, cut, edit, editm, kids, cols, t2j; j2t's overflow
  * rerun takes copy / sync and the destructor only), made
  * after Entry: the layout (host_layout.h) in vectors it owns, their upload into
  * the context's staging buffers, the packing and the download. Every copy is

@@ -1,4 +1,7 @@
-"""thrift/generic on the GPU. Batched SetMany (EditManyPlan, set_many_batch,
+"""thrift/generic on the GPU. Typed column reads (the last part of this
+module: ColumnPlan, columns_batch, columns_device, column_list_device:
+GetByPath followed by Node.Int / Float64 / String / List ... as tensors),
+batched SetMany (EditManyPlan, set_many_batch,
 unset_many_batch, edit_many_device: several children of one node edited in one
 pass), batched Children (the fourth part of this
 module: children_batch, children_records, children_device), batched
@@ -959,3 +962,154 @@ def children_device(pathset: PathSet, thrift, in_off, n: int, head, rec_off, rec
     flags = (KIDS_F_RECURSE if recurse else 0) | (KIDS_F_COUNTED if counted else 0)
     _lib.check(_lib.lib().dg_kids_batch_device(pathset.ctx.h, pathset.h, root_type, flags, _ptr(thrift), _ptr(in_off), n,
                                                _ptr(head), _ptr(rec_off), _ptr(recs), rec_cap, s, max_len))
+
+
+# ---------------------------------------------------------------------------
+# Typed column reads: GetByPath followed by Node.Bool / Byte / Int / Float64 /
+# String / Len / List for every message of a batch
+# (thrift/generic/cast.go:50-224; dg_cols_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+COL_BOOL, COL_BYTE, COL_INT, COL_F64, COL_STR, COL_LEN, COL_LIST = 1, 2, 3, 4, 5, 6, 16  # DG_COL_*
+COL_LIST_INT, COL_LIST_F64 = COL_LIST | COL_INT, COL_LIST | COL_F64
+COL_E_UNSUPPORTED = 4  # DG_COL_E_UNSUPPORTED
+COL_ERROR_NAMES = dict(ERROR_NAMES)
+COL_ERROR_NAMES[COL_E_UNSUPPORTED] = "ErrUnsupportedType"
+COL_CELL_DTYPE = np.dtype([("status", "u1"), ("type", "u1"), ("step", "<u2"), ("aux", "<u4")])  # dg_col_cell
+_COL_KINDS = {"bool": COL_BOOL, "byte": COL_BYTE, "int": COL_INT, "float64": COL_F64, "str": COL_STR, "len": COL_LEN,
+              "list[int]": COL_LIST_INT, "list[float64]": COL_LIST_F64}
+
+
+def col_kind(kind) -> int:
+    """A kind as DG_COL_* or by name: bool, byte, int, float64, str, len, list[int], list[float64]."""
+    k = _COL_KINDS.get(kind, kind)
+    if k not in _COL_KINDS.values():
+        raise ValueError("unknown column kind %r" % (kind,))
+    return int(k)
+
+
+class ColumnPlan(_Handle):
+    """1 to 8 columns, each a path (a list of Path steps; PathFieldName is
+    resolved through `desc`) and a kind (col_kind), on one context's device
+    (dg_cols). `columns` is a list of (path, kind)."""
+    _destroy = "dg_cols_destroy"
+
+    def __init__(self, columns, desc=None, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.kinds = [col_kind(k) for _, k in columns]
+        self.blob = compile_paths([p for p, _ in columns], desc)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dg_cols_create(self.ctx.h, self.blob, len(self.blob), bytes(self.kinds), len(self.kinds),
+                                             C.byref(h)))
+        self.h = h
+        self.count = int(_lib.lib().dg_cols_count(h))
+        self.lists = [k for k, kind in enumerate(self.kinds) if kind & COL_LIST]
+
+
+def columns_device(plan: ColumnPlan, thrift, in_off, n: int, val, cell, lens=None, root_type: int = STRUCT,
+                   stream=None, max_len: int = 0):
+    """The cell pass (dg_cols_batch_device) over torch tensors or raw device
+    pointers: thrift uint8[>= in_off[n] + 16]; in_off int64[n + 1]; val
+    int64[P, n] (a float64 column: val[k].view(torch.float64)); cell P * n
+    8-byte cells (e.g. int32 of shape (P, n, 2)); lens int32[P, n], None when
+    no column is str or a list. Column-major: a column is one contiguous
+    tensor. Asynchronous on `stream` (a torch stream, a raw stream handle, or
+    None for torch's current stream when `thrift` is a tensor)."""
+    s = _stream_handle(stream, thrift)
+    _lib.check(_lib.lib().dg_cols_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n, _ptr(val),
+                                               _ptr(cell), _ptr(lens), s, max_len))
+
+
+def column_list_device(plan: ColumnPlan, k: int, thrift, n: int, val_k, cell_k, len_k, elem_off, elems, elem_cap: int,
+                       stream=None):
+    """List column k's elements (dg_cols_list_device) behind columns_device on
+    the same stream: val_k / cell_k / len_k are column k's rows of its
+    outputs; elem_off int64[n + 1] receives the scanned counts ([n] = the
+    total); elems int64[elem_cap] (a float64 list: .view(torch.float64)) the
+    elements, or None to stop after the scan."""
+    s = _stream_handle(stream, thrift)
+    _lib.check(_lib.lib().dg_cols_list_device(plan.ctx.h, plan.h, k, _ptr(thrift), n, _ptr(val_k), _ptr(cell_k),
+                                              _ptr(len_k), _ptr(elem_off), _ptr(elems), elem_cap, s))
+
+
+class Column:
+    """One column of columns_batch: .kind; .status (uint8[n]: OK, NOT_FOUND,
+    E_READ, E_TYPE or COL_E_UNSUPPORTED), .valid (status == OK), .type,
+    .step, .aux (the cell's other fields), .error(i) (None, "ErrNotFound",
+    "ErrRead", "ErrDismatchType" or "ErrUnsupportedType"). .values by kind:
+    bool -> bool[n], byte -> uint8[n], int and len -> int64[n], float64 ->
+    float64[n] (0 where not valid); str -> a list of n bytes (b"" where not
+    valid), with .offsets / .lengths into the arena the messages form back to
+    back; list[int] / list[float64] -> all elements as int64 / float64, row
+    i's at .values[.offsets[i]:.offsets[i + 1]]."""
+    __slots__ = ("kind", "status", "valid", "type", "step", "aux", "values", "offsets", "lengths")
+
+    def error(self, i: int):
+        return COL_ERROR_NAMES.get(int(self.status[i]), "ErrRead")
+
+    def __repr__(self):
+        return "Column(kind=%d, %d cells, %d valid)" % (self.kind, len(self.status), int(self.valid.sum()))
+
+
+def columns_records(msgs: Sequence[bytes], plan: ColumnPlan, root_type: int = STRUCT):
+    """The raw outputs of dg_cols_batch_host: (val uint64[P, n], cell
+    COL_CELL_DTYPE[P, n], lens uint32[P, n], elem_off uint64[L, n + 1], elems
+    uint64[all elements], arena), L = len(plan.lists); STR and list values are
+    offsets into `arena`, the messages back to back."""
+    n, P, L = len(msgs), plan.count, len(plan.lists)
+    lib = _lib.lib()
+    val = np.zeros((P, n), dtype=np.uint64)
+    cell = np.zeros((P, n), dtype=COL_CELL_DTYPE)
+    lens = np.zeros((P, n), dtype=np.uint32)
+    elem_off = np.zeros((max(L, 1), n + 1), dtype=np.uint64)
+    need = C.c_uint64(0)
+    if n == 0:
+        _lib.check(lib.dg_cols_batch_host(plan.ctx.h, plan.h, root_type, None, None, 0, None, None, None,
+                                          elem_off.ctypes.data, None, 0, C.byref(need)))
+        return val, cell, lens, elem_off[:L], np.zeros(0, dtype=np.uint64), np.zeros(16, dtype=np.uint8)
+    arena, in_off = _arena(msgs)
+
+    def call(cap):
+        out = np.zeros(cap, dtype=np.uint64)
+        return lib.dg_cols_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
+                                      val.ctypes.data, cell.ctypes.data, lens.ctypes.data, elem_off.ctypes.data,
+                                      out.ctypes.data if cap else None, cap, C.byref(need)), out
+
+    # a guess the call corrects (an element takes at least one byte of its message, four as a rule)
+    elems = _until_fits(call, int(in_off[n]) // 4 + 64 if L else 0, need)
+    return val, cell, lens, elem_off[:L], elems[:int(need.value)], arena
+
+
+def columns_batch(msgs: Sequence[bytes], columns, desc=None, root_type: int = STRUCT,
+                  ctx: Optional[Context] = None) -> List[Column]:
+    """GetByPath and a cast for every message of a batch (dg_cols_batch_host):
+    `columns` is a list of (path, kind) or a ColumnPlan; one Column comes back
+    per path."""
+    plan = columns if isinstance(columns, ColumnPlan) else ColumnPlan(columns, desc, ctx)
+    with _unless_given(plan, columns):
+        n = len(msgs)
+        val, cell, lens, elem_off, elems, arena = columns_records(msgs, plan, root_type)
+        out = []
+        for k, kind in enumerate(plan.kinds):
+            c = Column()
+            c.kind, c.status, c.type, c.step, c.aux = kind, cell[k]["status"], cell[k]["type"], cell[k]["step"], cell[k]["aux"]
+            c.valid = c.status == OK
+            c.offsets = c.lengths = None
+            if kind & COL_LIST:
+                eo = elem_off[plan.lists.index(k)]
+                seg = elems[int(eo[0]):int(eo[n])]
+                c.values = seg.view(np.float64) if kind == COL_LIST_F64 else seg.view(np.int64)
+                c.offsets, c.lengths = (eo - eo[0]).astype(np.int64), lens[k]
+            elif kind == COL_STR:
+                c.offsets, c.lengths = val[k].astype(np.int64), lens[k]
+                c.values = [arena[int(o):int(o) + int(ln)].tobytes() if ok else b""
+                            for o, ln, ok in zip(c.offsets, c.lengths, c.valid)]
+            elif kind == COL_BOOL:
+                c.values = val[k] != 0
+            elif kind == COL_BYTE:
+                c.values = val[k].astype(np.uint8)
+            elif kind == COL_F64:
+                c.values = val[k].view(np.float64)
+            else:
+                c.values = val[k].view(np.int64)
+            out.append(c)
+        return out

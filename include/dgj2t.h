@@ -90,6 +90,8 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *                                 is emitted one lane per record (256; 0 = never)
  *   "kids_no_scan" (no env)       timing only: 1 = dg_kids_* calls leave the scan out, so d_rec_off is not written
  *                                 (tools/kids_bench.py times the count pass alone with it, without d_recs)
+ *   "cols_full_search" (no env)   timing only: 1 = every lane of dg_cols_list_device's emit searches all n offsets
+ *                                 for its message (0: between the answers of its block's first and last lane)
  *   "edit_reuse_rec" (no env)     timing only: 1 = an edit launch of as many messages as the context's previous
  *                                 one skips the lookup and splices from its records (tools/edit_bench.py times the
  *                                 splice alone with it; another batch or path gives undefined results;
@@ -860,6 +862,89 @@ int dg_kids_batch_device(dg_ctx *ctx, const dg_path *path, uint8_t root_type, ui
 int dg_kids_batch_host(dg_ctx *ctx, const dg_path *path, uint8_t root_type, uint32_t flags, const uint8_t *thrift,
                        const uint64_t *in_off, uint64_t n, dg_kids_head *head, uint64_t *rec_off, dg_kid_rec *recs,
                        uint64_t rec_cap, uint64_t *need);
+
+/* ------------------------------------------------------------------------
+ * cols: typed column reads over Thrift-binary messages: GetByPath followed by
+ * the reference's casts (thrift/generic/cast.go:50-224). A column is one path
+ * plus a kind (dgj2t_defs.h DG_COL_*); cell (i, k) is what
+ * v.GetByPath(path_k...) on message i and then the cast of column k's kind
+ * give. A plan holds 1 to DG_TGET_MAX_PATHS columns; dg_cols_create takes
+ * dg_path_create's blob with its limits and texts and n_kinds kinds, one per
+ * path (DG_E_ARG with a text for an unknown kind or another count).
+ *
+ * A cell is a value (8 bytes), a dg_col_cell and, for STR and list columns, a
+ * length:
+ *   the lookup fails   status DG_TGET_NOT_FOUND / E_READ / E_TYPE with the
+ *                      type, step and aux dg_tget_rec would hold; value 0.
+ *   the cast does not take the wire type found
+ *                      DG_COL_E_UNSUPPORTED (meta.ErrUnsupportedType), type =
+ *                      the wire type found, step = the path length; value 0.
+ *   DG_COL_BOOL        BOOL: 1 if the byte is exactly 1, else 0 (DecodeBool).
+ *   DG_COL_BYTE        I08: the byte, 0..255.
+ *   DG_COL_INT         I08 UNSIGNED (Node.Int goes through DecodeByte: 0x80 is
+ *                      128); I16, I32, I64 big-endian, sign-extended.
+ *   DG_COL_F64         DOUBLE: the 8 bytes byte-swapped, nothing else (NaN
+ *                      payloads, -0.0 and denormals survive as bits).
+ *   DG_COL_STR         STRING: value = the payload's offset in the arena
+ *                      (d_in_off[i] + start + 4), length = end - start - 4:
+ *                      the (offset, length) pair dg_pack_device_scan takes.
+ *   DG_COL_LEN         LIST, SET: the i32 count at start + 1; MAP: at start + 2.
+ *   DG_COL_LIST | DG_COL_INT, DG_COL_LIST | DG_COL_F64
+ *                      for e in node.List(): e.Int() / e.Float64(). The node
+ *                      must be LIST or SET (else E_UNSUPPORTED). Its header is
+ *                      read as ReadListBegin reads it: an element type that
+ *                      is not Valid() is DG_TGET_E_READ, step = the path
+ *                      length, at any size. Size 0 with a valid element type:
+ *                      OK, length 0. A non-empty list whose element type the
+ *                      cast rejects (INT: anything but I08 / I16 / I32 / I64;
+ *                      F64: anything but DOUBLE): E_UNSUPPORTED, type = the
+ *                      node's, aux = the element type, no elements: a cell is
+ *                      whole or empty. OK: length = the element count, value =
+ *                      the arena offset of element 0, type = the element type.
+ *                      Elements come out 8 bytes each: INT extended per width
+ *                      (I08 unsigned), F64 bit for bit.
+ * Elsewhere the length is 0. The reference's List() builds interface values
+ * element by element and stops at the first that fails; here the element
+ * type is checked once, in the header.
+ */
+typedef struct dg_cols dg_cols;
+int dg_cols_create(dg_ctx *ctx, const void *path_blob, size_t len, const uint8_t *kinds, uint32_t n_kinds,
+                   dg_cols **out);
+void dg_cols_destroy(dg_cols *p);
+uint32_t dg_cols_count(const dg_cols *p);
+
+/* The cell pass. Device buffers, stream-ordered, async (stream NULL: the
+ * context's); messages, root_type, the 16 readable bytes past the arena's end
+ * and n * P < 2^32 as dg_tget_batch_device. Outputs are column-major, P = the
+ * plan's column count: d_val (u64) and d_cell (dg_col_cell) hold P * n entries,
+ * column k at [k * n, k * n + n), both 8-byte aligned; d_len (u32, P * n) may
+ * be NULL when no column is STR or a list. n = 0 returns DG_OK and launches
+ * nothing. Pairs nested beyond the 8 LDS skip frames are rerun by a deep pass
+ * whose queue, counters and frames are the component's own. max_len: a hint. */
+int dg_cols_batch_device(dg_ctx *ctx, const dg_cols *cols, uint8_t root_type, const uint8_t *d_thrift,
+                         const uint64_t *d_in_off, uint64_t n, uint64_t *d_val, dg_col_cell *d_cell, uint32_t *d_len,
+                         void *stream, uint64_t max_len);
+/* The elements of list column k after dg_cols_batch_device on the same stream
+ * (or ordered behind it): d_val_k / d_cell_k / d_len_k are column k's parts of
+ * its outputs (d_val + k * n, ...). A scan of the counts fills d_elem_off (u64,
+ * n + 1 entries, [n] = the total); then message i's elements go to
+ * d_elems[d_elem_off[i], d_elem_off[i + 1]), 8 bytes each; empty and failed
+ * cells contribute nothing. d_elems NULL stops after the scan (sizing). No
+ * element is stored at an index >= elem_cap. DG_E_ARG when k names no list
+ * column. */
+int dg_cols_list_device(dg_ctx *ctx, const dg_cols *cols, uint32_t k, const uint8_t *d_thrift, uint64_t n,
+                        const uint64_t *d_val_k, const dg_col_cell *d_cell_k, const uint32_t *d_len_k,
+                        uint64_t *d_elem_off, uint64_t *d_elems, uint64_t elem_cap, void *stream);
+/* Host buffers, synchronous (no spare bytes needed): val, cell and len (never
+ * NULL here) as above, offsets relative to `thrift`. With L list columns,
+ * elem_off has L * (n + 1) entries, the j-th list column's at [j * (n + 1), ...):
+ * its message i owns elems[elem_off[i], elem_off[i + 1]), the columns' elements
+ * one after the other, and *need = the last entry = all elements. elems NULL
+ * with elem_cap 0 stops there (sizing); otherwise DG_E_NOMEM when elem_cap <
+ * *need. elem_off may be NULL when L = 0. */
+int dg_cols_batch_host(dg_ctx *ctx, const dg_cols *cols, uint8_t root_type, const uint8_t *thrift,
+                       const uint64_t *in_off, uint64_t n, uint64_t *val, dg_col_cell *cell, uint32_t *len,
+                       uint64_t *elem_off, uint64_t *elems, uint64_t elem_cap, uint64_t *need);
 
 /* Timing helper for benchmarks: launch the device batch `iters` times on the
  * context stream bracketed by HIP events; returns total milliseconds of GPU

@@ -289,6 +289,27 @@ typedef struct dg_kids_head {
     uint8_t status;
 } dg_kids_head; /* 16 bytes */
 
+/* cols (typed column reads, include/dgj2t.h dg_cols_*): a column's kind is
+ * the cast behind the lookup; DG_COL_LIST | DG_COL_INT and DG_COL_LIST |
+ * DG_COL_F64 are the two list kinds. A cell's status is the lookup's
+ * (DG_TGET_*) or DG_COL_E_UNSUPPORTED. */
+#define DG_COL_BOOL 1u  /* Node.Bool */
+#define DG_COL_BYTE 2u  /* Node.Byte */
+#define DG_COL_INT 3u   /* Node.Int */
+#define DG_COL_F64 4u   /* Node.Float64 */
+#define DG_COL_STR 5u   /* Node.String / Node.Binary */
+#define DG_COL_LEN 6u   /* Node.Len */
+#define DG_COL_LIST 16u /* Node.List, each element through Int or Float64 */
+#define DG_COL_E_UNSUPPORTED 4u /* meta.ErrUnsupportedType: the cast does not take the wire type found (the value of
+                                   DG_KIDS_E_UNSUPPORTED) */
+typedef struct dg_col_cell {
+    uint8_t status; /* DG_TGET_OK / NOT_FOUND / E_READ / E_TYPE or DG_COL_E_UNSUPPORTED */
+    uint8_t type;   /* the wire type found (OK and E_UNSUPPORTED; an OK list cell: its element type); a failed lookup:
+                       dg_tget_rec's type */
+    uint16_t step;  /* dg_tget_rec's step */
+    uint32_t aux;   /* dg_tget_rec's aux; a list whose element type the cast rejects: that element type */
+} dg_col_cell; /* 8 bytes */
+
 /* t2j (Thrift binary -> JSON, conv/t2j) option bits: the conv.Options fields
  * conv/t2j/impl.go reads (conv/api.go:52-121) */
 #define DG_T2J_BYTE_AS_UINT8 (1ull << 0)     /* ByteAsUint8 */
