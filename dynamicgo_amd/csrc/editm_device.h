@@ -14,19 +14,23 @@
  *
  * (g_0 = 0, g_c = the end of cut c - 1) and at last msg[g_K, len), with the
  * container's 4-byte count, which lies in front of the first cut, replaced.
- * em_splice keeps ed_splice's discipline: 16-byte units aligned on the
- * DESTINATION, each assembled by em_fetch from every run that covers it (up to
- * 4 K + 1), head and tail clipped to the byte, no byte stored twice.
+ * em_splice writes it in 16-byte units aligned on the DESTINATION, each
+ * assembled by em_fetch from every run that covers it (up to 4 K + 1; the
+ * patched count is folded in before the store), so a store never mixes lanes
+ * and no byte is stored twice. The head up to the first boundary and the tail
+ * after the last are clipped to the byte.
  *
  * Everything is a template over K: every index into the table is a constant once
  * the loops are unrolled, so the table lives in registers (a private array
  * indexed by a variable goes to scratch memory). The K cuts are sorted by a
- * bubble network of compare-exchanges for the same reason. Compiles for the host
- * like edit_device.h (EDI, TGI).
+ * bubble network of compare-exchanges for the same reason. The lanes that share
+ * a message are a template parameter too (1, 4 or 16: the lane route, 64: the
+ * wave route). Compiles for the host like edit_device.h (EDI, TGI).
  *
  * Bounds: as edit_device.h. Reads run at most 15 bytes past a run's end (message
  * and value arenas readable 16 bytes past their ends, 16 zero bytes after the
- * path blob); writes are exactly [dst, dst + out_len), and only when it fits.
+ * path blob); writes are exactly [dst, dst + out_len), and only when out_len
+ * fits the slot.
  */
 #pragma once
 #include "edit_device.h"
@@ -238,7 +242,9 @@ EDI void em_splice(const EmSrc<KT> &S, uint8_t *d, uint32_t lane)
     }
 }
 
-/* message i for lane `lane` of the LANES that share it, as edit_message */
+/* message i for lane `lane` of the LANES that share it (WAVE: the wave route,
+ * else the lane route with 1, 4 or 16 lanes a message); a message whose route
+ * is the other one is left to it. Lane 0 stores out_len and ret. */
 template <uint32_t KT, uint32_t LANES, bool WAVE>
 EDI void editm_message(const EmParams &A, uint64_t i, uint32_t lane)
 {
@@ -249,6 +255,8 @@ EDI void editm_message(const EmParams &A, uint64_t i, uint32_t lane)
     TGRes full[KT];
     const uint8_t *vp[KT];
     uint64_t vl[KT];
+    /* the lookup's spans lie inside the message; records of another batch (the
+     * edit_reuse_rec knob misused) must not take a read outside it */
     bool sane = par.start <= par.end && par.end <= len;
 #pragma unroll
     for (uint32_t j = 0; j < KT; j++) {

@@ -1,14 +1,18 @@
-/* editm kernels (batched SetMany, editm_device.h): the splice's lane route and
- * wave route, as edit_kern.hip's, instantiated per item count K = 1..7 so that
- * the segment table of K cuts is indexed by constants only and stays in
- * registers. Both read the lookup's K + 1 records per message, take the same
- * decision and leave a message to the other kernel when its output length puts
- * it there (EmParams::wave_min). */
+/* edit kernels (batched SetMany, and SetByPath / UnsetByPath as its K = 1;
+ * editm_device.h): the splice's lane route and wave route, instantiated per
+ * item count K = 1..7 so that the segment table of K cuts is indexed by
+ * constants only and stays in registers. Both read the lookup's K + 1 records
+ * per message, take the same decision and leave a message to the other kernel
+ * when its output length puts it there (EmParams::wave_min), so no queue is
+ * needed: the decision costs K + 1 16-byte records and at most one 16-byte
+ * window of the message per item. */
 #include "editm_device.h"
 
 namespace dg {
 
-/* G lanes per message (1, 4 or 16) take the aligned 16-byte units of its output in turn */
+/* G lanes per message (1, 4 or 16) take the aligned 16-byte units of its output
+ * in turn, so G neighbouring lanes store G x 16 contiguous bytes; with G = 1 a
+ * lane assembles and stores every unit of its message itself */
 template <uint32_t KT, uint32_t G>
 __global__ __launch_bounds__(ED_BLOCK) void editm_lane_kernel(EmParams A)
 {
@@ -17,9 +21,10 @@ __global__ __launch_bounds__(ED_BLOCK) void editm_lane_kernel(EmParams A)
     editm_message<KT, G, false>(A, i, threadIdx.x % G);
 }
 
-/* one wave per message, a fixed grid striding over the batch; the message index
- * comes from readfirstlane: the records, the decision and the table are
- * wave-uniform */
+/* one wave per message, a fixed grid striding over the batch: the 64 lanes take
+ * the output's aligned 16-byte units in turn, so a wave's stores are one
+ * contiguous KiB; the message index comes from readfirstlane: the records, the
+ * decision and the table are wave-uniform */
 template <uint32_t KT>
 __global__ __launch_bounds__(ED_WAVES * 64) void editm_wave_kernel(EmParams A)
 {

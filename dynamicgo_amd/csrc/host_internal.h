@@ -5,7 +5,7 @@
  * per-stream scratch records, the entry guard, the argument records of one
  * batch, the host batch of the thrift/generic and t2j entries (HostBatch) and the
  * error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host, edit_host, editm_host, kids_host, cols_host and j2t_pipe
+ * tget_host, cut_host, editm_host, kids_host, cols_host and j2t_pipe
  * use them).
  */
 #pragma once
@@ -273,9 +273,9 @@ struct Knobs {
     int64_t flat_wrap = -1;     /* the flat kernel's wrapped mode for roots that wrap a flat struct (0: off) */
     int64_t tget_spread = 0;    /* tget: lanes per (message, path) pair, 0 = from the longest message (tget_host.hip) */
     int64_t cut_wave_min = 4096; /* cut: messages at least this long take the wave route (0: all of them); ~1.1 KB x 65 536: 256 / 1024 / 4096 / 16384 -> 29.5 / 44.0 / 227.2 / 227.6 GB/s; ~83 KB x 4 096: lane 23.5, wave 26.5 */
-    int64_t edit_reuse_rec = 0;   /* edit, timing only: 1 = a launch of as many messages as the context's previous edit launch skips the lookup and splices from its records (the same batch and path, or the result is undefined) */
-    int64_t edit_lanes = 4;       /* edit: lanes per message on the splice's lane route, 1, 4 or 16 (anything else: 1); splice alone at 1 / 4 / 16, ~227 B x 65 536: 264 / 300 / 254 GB/s, ~1.1 KB x 65 536: 607 / 882 / 908, ~83 KB x 4 096: 47 / 203 / 690 */
-    int64_t edit_wave_min = 4096; /* edit: outputs at least this long take the splice's wave route (0: all of them); ~1.1 KB x 65 536 at 4 lanes, 256 / 1024 / 4096 / 16384 -> 556 / 502 / 884 / 882 GB/s; ~83 KB x 4 096: lane route 203, wave route 1 407 */
+    int64_t edit_reuse_rec = 0;   /* edit and editm, timing only: 1 = a launch of as many messages and items as the context's previous edit launch skips the lookup and splices from its records (the same batch and paths, or the result is undefined) */
+    int64_t edit_lanes = 4;       /* edit: lanes per message on the splice's lane route, 1, 4 or 16 (anything else: 1); splice alone at 1 / 4 / 16, ~227 B x 65 536: 259 / 291 / 264 GB/s, ~1.1 KB x 65 536: 593 / 876 / 978, ~83 KB x 4 096: 54 / 250 / 814 */
+    int64_t edit_wave_min = 4096; /* edit: outputs at least this long take the splice's wave route (0: all of them); ~1.1 KB x 65 536 at 4 lanes, 256 / 1024 / 4096 / 16384 -> 588 / 546 / 877 / 875 GB/s; ~83 KB x 4 096: lane route 250, wave route 1 550 */
     int64_t kids_wide_min = 256;  /* kids: a list, set or map node of fixed-size entries with at least this many children is emitted by the record-parallel kernel (0: never); emit pass, 16 384 x list<i64> of 64 / 128 / 256 / 1024, lane route 0.107 / 0.159 / 0.261 / 1.314 ms, wide route 0.264 / 0.270 / 0.278 / 0.350 */
     int64_t kids_no_scan = 0;     /* kids, timing only: 1 = a call leaves the scan out (rec_off is not written) */
     int64_t cols_full_search = 0; /* cols, timing only: 1 = every lane of the list emit searches all n offsets (0: between the answers of its block's first and last lane) */
@@ -321,16 +321,11 @@ struct dg_ctx {
     StreamOrder cut;
     DevArr<uint32_t> cut_list, cut_cnt_buf;
     AltCounters cut_cnt;
-    /* edit (edit_host.hip): the lookup's 2 n records of one batch, ordered
-     * across streams like tget's workspace */
+    /* edit and editm (editm_host.hip): the lookup's (K + 1) n records of one
+     * batch, ordered across streams like tget's workspace */
     StreamOrder edit;
     DevArr<dg_tget_rec> edit_rec;
-    uint64_t edit_rec_n = 0; /* messages of the launch that filled edit_rec */
-    /* editm (editm_host.hip): the lookup's (K + 1) n records of one batch, a
-     * scratch of its own so that edit_rec keeps what the edit_reuse_rec knob
-     * promises */
-    StreamOrder editm;
-    DevArr<dg_tget_rec> editm_rec;
+    uint64_t edit_rec_n = 0, edit_rec_k = 0; /* messages and items of the launch that filled edit_rec */
     /* kids (kids_host.hip): the deep pass's frames (32 MB, allocated by the
      * first call), the deep and wide queues (n entries each), the two
      * alternating counter sets {deep, wide} and the scan's tile sums */

@@ -92,10 +92,10 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *                                 (tools/kids_bench.py times the count pass alone with it, without d_recs)
  *   "cols_full_search" (no env)   timing only: 1 = every lane of dg_cols_list_device's emit searches all n offsets
  *                                 for its message (0: between the answers of its block's first and last lane)
- *   "edit_reuse_rec" (no env)     timing only: 1 = an edit launch of as many messages as the context's previous
- *                                 one skips the lookup and splices from its records (tools/edit_bench.py times the
- *                                 splice alone with it; another batch or path gives undefined results;
- *                                 dg_editm_* keeps records of its own and does not look at it)
+ *   "edit_reuse_rec" (no env)     timing only: 1 = a dg_edit_* or dg_editm_* launch of as many messages and items as
+ *                                 the context's previous one skips the lookup and splices from its records
+ *                                 (tools/edit_bench.py times the splice alone with it; another batch or other
+ *                                 paths give undefined results)
  * Unknown names return DG_E_INVALID. Thread-safe (the context lock). */
 int dg_ctx_set_knob(dg_ctx *ctx, const char *name, int64_t value);
 int dg_ctx_get_knob(dg_ctx *ctx, const char *name, int64_t *value);
@@ -719,8 +719,8 @@ uint64_t dg_edit_slot_bound(const dg_edit *e, uint64_t len, uint64_t val_len);
  * take by the two hints, so a hint that is given must not be too small: a
  * message longer than it may be left unwritten. n = 0 returns DG_OK and
  * launches nothing.
- * The lookup's 2 n records live in a scratch of the context, ordered across
- * streams like the lookup's own workspace. Two routes: "edit_lanes" lanes per
+ * The lookup's 2 n records live in a scratch of the context, the one dg_editm_*
+ * uses, ordered across streams like the lookup's own workspace. Two routes: "edit_lanes" lanes per
  * message (1, 4 or 16), and a wave per message for outputs at least
  * "edit_wave_min" bytes long. */
 int dg_edit_batch_device(dg_ctx *ctx, const dg_edit *e, uint8_t root_type, const uint8_t *d_thrift,
@@ -794,8 +794,9 @@ uint64_t dg_editm_slot_bound(const dg_editm *e, uint64_t len, uint64_t val_total
  * message-major) item j of message i is d_val[d_val_off[i*K+j], d_val_off[i*K+j+1])
  * and val_lens[j] is the longest value of item j, a hint (0 = unknown); with
  * d_val_off NULL d_val holds the K values back to back (val_lens[j] bytes each)
- * and every message gets them. The lookup's (K + 1) n records live in a scratch
- * of the context of their own, ordered across streams. */
+ * and every message gets them. The lookup's (K + 1) n records live in the
+ * scratch of the context that dg_edit_* uses too (it is this call with K = 1),
+ * ordered across streams. */
 int dg_editm_batch_device(dg_ctx *ctx, const dg_editm *e, uint8_t root_type, const uint8_t *d_thrift,
                           const uint64_t *d_in_off, uint64_t n, const uint8_t *val_types, const uint8_t *d_val,
                           const uint64_t *d_val_off, const uint64_t *val_lens, uint8_t *d_out,

@@ -1,7 +1,8 @@
-/* The edit's decision function and splice (dynamicgo_amd/csrc/edit_device.h)
+/* The edit's decision function (dynamicgo_amd/csrc/edit_device.h) and the
+ * many-edit's splice with one item (editm_device.h), as dg_edit_* runs them,
  * built for the host, behind the lookup's walk (tget_device.h) as the launch
  * sequence runs them: tg_walk on (parent, full) with 8 frames, then 1024 where
- * that ends TG_ST_DEEP, then edit_message. route 0 is the lane route (one lane
+ * that ends TG_ST_DEEP, then editm_message<1>. route 0 is the lane route (one lane
  * writes everything), route 1 the wave route, run once per lane 0..63 into the
  * same output, each lane writing its share; routes 2 and 3 are the lane route
  * with 4 and 16 lanes a message, run the same way. test_edit_host.py loads it; with
@@ -10,7 +11,7 @@
  * len + 16 bytes) for a sanitizer to watch. */
 #define TGI inline
 #define EDI inline
-#include "../dynamicgo_amd/csrc/edit_device.h"
+#include "../dynamicgo_amd/csrc/editm_device.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -46,23 +47,24 @@ extern "C" void edit_msg(const uint8_t *msg, uint64_t len, const uint8_t *blob, 
     memcpy(&last, blob + h.off_steps + (uint64_t)(pe.first + pe.count - 1) * sizeof last, sizeof last);
     const bool pooled = last.kind == DG_PS_STRKEY || last.kind == DG_PS_BINKEY;
     const uint64_t in_off[2] = {0, len}, out_off[2] = {0, cap};
-    dg::EditParams A = {};
-    A.step = dg::EditStep{op, pe.count, last.kind, last.key_len, last.val, val_type};
-    A.key = blob + h.off_pool + (pooled ? last.val : 0);
+    dg::EmParams A = {};
+    A.op = op, A.n_steps = pe.count, A.K = 1;
+    A.it[0] = dg::EmItem{last.kind, last.key_len, last.val, val_type, h.off_pool + (pooled ? (uint32_t)last.val : 0u), 0, vlen};
+    A.pool = blob;
     A.src = msg, A.in_off = in_off, A.n = 1, A.rec = rec;
-    A.val = val, A.val_len = vlen;
+    A.val = val;
     A.out = out, A.out_off = out_off, A.out_len = out_len, A.ret = ret;
     if (route == 1) {
         A.wave_min = 0;
-        for (uint32_t lane = 0; lane < 64; lane++) dg::edit_message<64, true>(A, 0, lane);
+        for (uint32_t lane = 0; lane < 64; lane++) dg::editm_message<1, 64, true>(A, 0, lane);
         return;
     }
     A.wave_min = ~0ull;
-    if (route == 0) dg::edit_message<1, false>(A, 0, 0);
+    if (route == 0) dg::editm_message<1, 1, false>(A, 0, 0);
     else if (route == 2)
-        for (uint32_t lane = 0; lane < 4; lane++) dg::edit_message<4, false>(A, 0, lane);
+        for (uint32_t lane = 0; lane < 4; lane++) dg::editm_message<1, 4, false>(A, 0, lane);
     else
-        for (uint32_t lane = 0; lane < 16; lane++) dg::edit_message<16, false>(A, 0, lane);
+        for (uint32_t lane = 0; lane < 16; lane++) dg::editm_message<1, 16, false>(A, 0, lane);
 }
 
 #ifdef EDIT_MAIN

@@ -1,6 +1,7 @@
 """CPU: the edit checker (editref.py) pinned to the reference's own tests and to
 hand-written messages, dg_edit_create's refusals, the slot bound, and the
-decision function and splice of dynamicgo_amd/csrc/edit_device.h built for the
+decision function of dynamicgo_amd/csrc/edit_device.h and the many-edit's
+splice with one item (editm_device.h), as dg_edit_* runs them, built for the
 host (edit_host.cpp: every route, lane by lane) against the
 checker, once more as a stand-alone program under AddressSanitizer and UBSan."""
 import ctypes as C

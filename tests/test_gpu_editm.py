@@ -289,9 +289,12 @@ def test_each_kernel_leaves_the_others_messages_alone(knob, fuzz):
         on_every_route(knob, c, routes=(("both, 1 lane", 300, 1), ("both, 4 lanes", 300, 4), ("both, 16 lanes", 300, 16)))
 
 
-# 9 --------------------------------------------------- the existing kernels
+# 9 ------------------------------------------------------- the single edit
 def test_one_item_equals_the_single_edit_kernel(knob):
-    """K = 1 against dg_edit_batch_device on the same batch: word for word, byte for byte"""
+    """dg_edit_batch_device is dg_editm_batch_device with K = 1, so this compares one kernel reached through two
+    entries: it pins the single edit's argument mapping (val_type, val_len, the value offsets, the path set of
+    dg_edit_create) on every route, word for word, byte for byte. Both entries are judged by both independent
+    restatements, the many-edit checker (editmref) and the single-edit checker (editref), not by each other."""
     import test_gpu_edit as TE
     for c in G.fuzz_cases()[::3]:
         mc = MG.ManyCase(c.op, c.path[:-1], [(c.path[-1], c.values, c.val_type)], c.msgs, c.root_type, c.what)
@@ -301,7 +304,8 @@ def test_one_item_equals_the_single_edit_kernel(knob):
                 knob("edit_lanes", lanes)
                 single = TE.run_device(c, p1)
                 same(Batch(mc).run(pm), single, mc, "against dg_edit, " + name)
-                same(single, mc.want(), mc, "dg_edit against the many-edit checker")
+                same(single, mc.want(), mc, "dg_edit against the many-edit checker, " + name)
+                same(single, c.want(), c, "dg_edit against the single-edit checker, " + name)
 
 
 def test_four_items_equal_four_chained_single_edits(knob, fuzz):

@@ -1,13 +1,14 @@
 """GPU: what the batch size and the stream, not the message, decide in the cut
 (batched MarshalTo) and the edit (batched SetByPath / UnsetByPath): the wave
 kernels' stride loops over a queue or a batch longer than their grid
-(cut_kern.hip, edit_kern.hip; the grids are set in cut_host.hip and, for
-edit_host.hip, in host_internal.h), launches of one context with no synchronisation between them on
+(cut_kern.hip, editm_kern.hip; the grids are set in cut_host.hip and, for
+editm_host.hip, in host_internal.h), launches of one context with no synchronisation between them on
 one stream and on several (the cut queue's two counters, the events that order
 the streams), the queue and the record scratch growing while the launch before
-may still use the old ones, and an edit interleaved with a GetByPath, whose
+may still use the old ones, single edits and a many-edit on two streams, which
+share that record scratch, and an edit interleaved with a GetByPath, whose
 scratch its lookup shares. Every message's ret, out_len and bytes are compared
-with the checkers' (cutref.py, editref.py, tgetref.py); so are the guard bytes
+with the checkers' (cutref.py, editref.py, editmref.py, tgetref.py); so are the guard bytes
 around the slots and the fill behind every out_len.
 
 The big batches cycle through a few dozen distinct short messages, a number
@@ -24,7 +25,10 @@ import cutgen as CG
 import cutref as CR
 import descgen
 import editgen as EG
+import editmgen as MG
+import editmref as M
 import editref as E
+import slotguard as SG
 import t2jgen
 import tgetref as R
 from test_gpu_tget import expect as tget_expect, to_paths
@@ -32,7 +36,7 @@ from test_gpu_tget_deep import Outputs, Upload, launch as tget_launch
 
 pytestmark = pytest.mark.gpu
 
-FILL, GUARD = 0xEE, 64
+FILL, GUARD = 0xEE, SG.GUARD
 F = R.FIELD
 # the wave kernels' grids: min(ceil(n / WAVES), factor * CU) blocks of WAVES waves
 CUT_GRID_FACTOR = 4   # cut_host.hip, cut_launch: `(uint64_t)c->n_cu * 4`
@@ -385,6 +389,60 @@ def test_queue_and_records_grow_while_a_launch_is_in_flight():
                 torch.cuda.synchronize()
                 for b in es:
                     b.verify(b.want(), E.out_len, True, "edit %d, fresh context, batch of %d" % (op, b.n))
+    finally:
+        ctx.close()
+
+
+# ------------------------- single edits and a many-edit on two streams
+def test_single_and_many_edits_share_the_record_scratch_across_streams():
+    """dg_edit and dg_editm keep their lookup's records in one scratch of the context. On a context of its own, 257
+    fuzz messages (a block of the lane route and one lane more), with no synchronisation: a single SET on stream A
+    (2 n records), a many-SET of 7 items on stream B, which outgrows the scratch (8 n) while A's splice may still
+    read it, and a single UNSET on A, which has to wait for B's splice before its lookup writes over B's records;
+    the second round starts on the grown scratch behind the first one's UNSET. Every slot has its exact bound,
+    so the slot bases are unaligned and each neighbour's first byte is a guard."""
+    import torch
+    from dynamicgo_amd import generic as X
+    from dynamicgo_amd.conv import Context
+    n = 257
+    msgs = EG.fuzz_cases()[0].msgs[:n]
+    v1 = EG.wstr(b"x" * 33)
+    seven = [((F, k), v, t) for k, v, t in ((1, b"\x01", R.BOOL), (2, b"\x7f", R.BYTE), (3, b"\x01\x02", R.I16),
+                                           (4, struct.pack(">i", -1024), R.I32), (5, struct.pack(">q", 1 << 40), R.I64),
+                                           (6, struct.pack(">d", 0.5), R.DOUBLE), (22, struct.pack(">d", 0.5), R.DOUBLE))]
+    many = MG.ManyCase(M.SET_OP, [], seven, msgs)
+    wants = [[E.edit(E.SET_OP, m, [(F, 18)], v1, R.STRING) for m in msgs], many.want(),
+             [E.edit(E.UNSET_OP, m, [(F, 19)], b"", 0) for m in msgs]]
+    assert {r & 0xFF for r, _ in wants[0]} >= {E.OK, E.E_READ} and {r & 0xFF for r, _ in wants[1]} >= {M.OK, M.E_READ}
+    assert sum(r == E.word(E.OK, existed=True) for r, _ in wants[2]) > n // 4
+    caps = [[E.slot_bound(E.SET_OP, [(F, 18)], len(m), len(v1)) for m in msgs], [many.bound(i) for i in range(n)],
+            [len(m) for m in msgs]]
+    vals = b"".join(v for _, v, _ in seven)
+
+    def dev(b):
+        return torch.from_numpy(np.frombuffer(b + b"\0" * 16, dtype=np.uint8).copy()).cuda()
+
+    d_v1, d_v7 = dev(v1), dev(vals)
+    ctx = Context(0)  # fresh: edit_rec has no capacity yet
+    try:
+        sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+        with X.EditPlan(EG.paths_of([(F, 18)]), E.SET_OP, ctx=ctx) as p_set, \
+                X.EditPlan(EG.paths_of([(F, 19)]), E.UNSET_OP, ctx=ctx) as p_unset, \
+                X.EditManyPlan([], EG.paths_of(many.steps), M.SET_OP, ctx=ctx) as p_many:
+            rounds = [[Batch(msgs, np.arange(n), c) for c in caps] for _ in range(2)]
+            torch.cuda.synchronize()  # the uploads and fills; nothing from here to the last launch
+            for a, b, c in rounds:
+                X.edit_device(p_set, a.arena, a.d_in, n, R.STRING, d_v1, None, a.d_out, a.d_oo, a.d_ol, a.d_ret,
+                              val_len=len(v1), stream=sa, max_len=a.max_len)
+                X.edit_many_device(p_many, b.arena, b.d_in, n, many.val_types, d_v7, None, [len(v) for _, v, _ in seven],
+                                   b.d_out, b.d_oo, b.d_ol, b.d_ret, stream=sb, max_len=b.max_len)
+                X.edit_device(p_unset, c.arena, c.d_in, n, 0, None, None, c.d_out, c.d_oo, c.d_ol, c.d_ret, stream=sa,
+                              max_len=c.max_len)
+            torch.cuda.synchronize()
+            for r, bs in enumerate(rounds):
+                for b, want, out_len, what in zip(bs, wants, (E.out_len, M.out_len, E.out_len),
+                                                  ("single SET on A", "many-SET on B", "single UNSET on A")):
+                    b.verify(want, out_len, True, "round %d, %s" % (r, what))
     finally:
         ctx.close()
 
