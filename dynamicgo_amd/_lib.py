@@ -29,7 +29,9 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_editm_batch_host",
            "dg_kids_batch_device", "dg_kids_batch_host",
            "dg_cols_create", "dg_cols_destroy", "dg_cols_count", "dg_cols_batch_device", "dg_cols_list_device",
-           "dg_cols_batch_host"]
+           "dg_cols_batch_host",
+           "dg_vals_create", "dg_vals_destroy", "dg_vals_count", "dg_vals_wire_type", "dg_vals_batch_device",
+           "dg_vals_batch_host"]
 
 _lib = None
 
@@ -139,6 +141,12 @@ def lib() -> C.CDLL:
         "dg_cols_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, u64]),
         "dg_cols_list_device": (i32, [vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
         "dg_cols_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, u64, P64]),
+        "dg_vals_create": (i32, [vp, C.c_char_p, u32, vp, C.POINTER(vp)]),
+        "dg_vals_destroy": (None, [vp]),
+        "dg_vals_count": (u32, [vp]),
+        "dg_vals_wire_type": (C.c_uint8, [vp, u32]),
+        "dg_vals_batch_device": (i32, [vp, vp, vp, u64, u64, vp, u64, vp, vp, vp]),
+        "dg_vals_batch_host": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, P64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -179,6 +187,12 @@ class HMEntry(C.Structure):
 class VMEntry(C.Structure):
     """dg_cb_entry (include/dgj2t_defs.h)"""
     _fields_ = [("off", C.c_uint32), ("count", C.c_uint32)]
+
+
+class ValCol(C.Structure):
+    """dg_val_col (include/dgj2t_defs.h)"""
+    _fields_ = [("val", C.c_void_p), ("len", C.c_void_p), ("src", C.c_void_p), ("elem_off", C.c_void_p),
+                ("elems", C.c_void_p), ("present", C.c_void_p)]
 
 
 class CBTables(C.Structure):

@@ -231,7 +231,7 @@ class Context:
         """A routing knob (dg_ctx_set_knob, include/dgj2t.h): "flat",
         "wave_min", "wave_occ", "small_mpw", "list_blocks", "t2j_spread",
         "t2j_wave_min", "flat_wrap", "tget_spread", "cut_wave_min", "edit_wave_min", "edit_lanes",
-        "kids_wide_min"."""
+        "kids_wide_min", "vals_lane_emit"."""
         _lib.check(_lib.lib().dg_ctx_set_knob(self.h, name.encode(), int(value)))
 
     def get_knob(self, name: str) -> int:

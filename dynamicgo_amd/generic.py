@@ -1,5 +1,7 @@
-"""thrift/generic on the GPU. Typed column reads (the last part of this
-module: ColumnPlan, columns_batch, columns_device, column_list_device:
+"""thrift/generic on the GPU. Typed column writes (the last part of this
+module: ValuePlan, values_batch, values_device, set_columns_batch,
+build_structs_batch: the NewNode* constructors over tensors), typed column
+reads (the part before it: ColumnPlan, columns_batch, columns_device, column_list_device:
 GetByPath followed by Node.Int / Float64 / String / List ... as tensors),
 batched SetMany (EditManyPlan, set_many_batch,
 unset_many_batch, edit_many_device: several children of one node edited in one
@@ -750,7 +752,8 @@ class EditManyResult:
             self.status, self.existed, self.item, self.aux, len(self.raw))
 
 
-def _editm_batch(msgs, plan: EditManyPlan, values, val_types, root_type: int) -> List[EditManyResult]:
+def _editm_batch(msgs, plan: EditManyPlan, values, val_types, root_type: int, encoded=None) -> List[EditManyResult]:
+    """encoded: (val, val_off) of values_batch instead of `values`"""
     n, k = len(msgs), plan.k
     L = _lib.lib()
     vt = np.asarray(val_types if val_types is not None else [0] * k, dtype=np.uint8)
@@ -762,7 +765,10 @@ def _editm_batch(msgs, plan: EditManyPlan, values, val_types, root_type: int) ->
     arena, in_off = _arena(msgs)
     val = val_off = None
     vtotal = 0
-    if values is not None:
+    if encoded is not None:
+        val, val_off = np.concatenate([encoded[0], np.zeros(16, dtype=np.uint8)]), encoded[1]
+        vtotal = int(val_off[n * k])
+    elif values is not None:
         if all(isinstance(v, (bytes, bytearray)) for v in values):
             vl[:] = [len(v) for v in values]
             val = np.frombuffer(b"".join(bytes(v) for v in values) + b"\0" * 16, dtype=np.uint8)
@@ -1113,3 +1119,198 @@ def columns_batch(msgs: Sequence[bytes], columns, desc=None, root_type: int = ST
                 c.values = val[k].view(np.int64)
             out.append(c)
         return out
+
+
+# ---------------------------------------------------------------------------
+# Typed column writes, the inverse of the reads above: tensors encoded to
+# Thrift-binary values (NewNodeBool ... NewNodeString / NewNodeList /
+# NewNodeSet) or whole struct messages (NewNodeStruct)
+# (thrift/generic/node.go:92-201; dg_vals_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+VAL_BOOL, VAL_I08, VAL_F64, VAL_I16, VAL_I32, VAL_I64, VAL_STR = 2, 3, 4, 6, 8, 10, 11  # the wire types
+VAL_LIST, VAL_SET = 0x40, 0x80  # DG_VAL_LIST, DG_VAL_SET
+VAL_OK, VAL_E_SIZE = 0, 1  # DG_VAL_*
+VALS_MAX_COLS = 16  # DG_VALS_MAX_COLS
+_VAL_KINDS = {"bool": VAL_BOOL, "byte": VAL_I08, "i8": VAL_I08, "f64": VAL_F64, "double": VAL_F64, "i16": VAL_I16,
+              "i32": VAL_I32, "i64": VAL_I64, "str": VAL_STR, "string": VAL_STR, "binary": VAL_STR}
+_VAL_ELEMS = (VAL_BOOL, VAL_I08, VAL_F64, VAL_I16, VAL_I32, VAL_I64)
+
+
+def val_kind(kind) -> int:
+    """A kind as DG_VAL_* or by name: bool, byte / i8, i16, i32, i64, f64 /
+    double, str / string / binary, ("list", elem) and ("set", elem) with elem
+    any of those but str."""
+    if isinstance(kind, (tuple, list)) and len(kind) == 2 and kind[0] in ("list", "set"):
+        elem = val_kind(kind[1])
+        if elem not in _VAL_ELEMS:
+            raise ValueError("unknown value kind %r" % (kind,))
+        return (VAL_LIST if kind[0] == "list" else VAL_SET) | elem
+    k = _VAL_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+    ok = isinstance(k, int) and (k == VAL_STR or k in _VAL_ELEMS or (
+        k & (VAL_LIST | VAL_SET) in (VAL_LIST, VAL_SET) and k & 0x3F in _VAL_ELEMS and k < 0x100))
+    if not ok:
+        raise ValueError("unknown value kind %r" % (kind,))
+    return int(k)
+
+
+class ValuePlan(_Handle):
+    """1 to 16 columns to write, each a kind (val_kind), on one context's
+    device (dg_vals). With `field_ids` (one int16 per column) the plan builds
+    struct messages: every item gets its field header and every message its
+    STOP; without, the items are bare values, what edit_many_device takes.
+    .wire_types: the columns' wire types (edit_many_device's val_types)."""
+    _destroy = "dg_vals_destroy"
+
+    def __init__(self, kinds, field_ids=None, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.kinds = [val_kind(k) for k in kinds]
+        self.field_ids = None if field_ids is None else [int(f) for f in field_ids]
+        if self.field_ids is not None and len(self.field_ids) != len(self.kinds):
+            raise ValueError("%d field ids for %d columns" % (len(self.field_ids), len(self.kinds)))
+        ids = None if self.field_ids is None else np.array(self.field_ids, dtype=np.int16)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dg_vals_create(self.ctx.h, bytes(self.kinds), len(self.kinds),
+                                             None if ids is None else ids.ctypes.data, C.byref(h)))
+        self.h = h
+        self.count = int(_lib.lib().dg_vals_count(h))
+        self.wire_types = [int(_lib.lib().dg_vals_wire_type(h, k)) for k in range(self.count)]
+
+
+_VAL_FIELDS = ("val", "len", "src", "elem_off", "elems", "present")
+
+
+def _val_cols(cols, count: int):
+    """dg_val_col[K] from per-column dicts (or tuples in _VAL_FIELDS' order) of tensors, arrays or raw pointers"""
+    if len(cols) != count:
+        raise ValueError("%d columns for a plan of %d" % (len(cols), count))
+    recs = (_lib.ValCol * count)()
+    for r, c in zip(recs, cols):
+        c = c if isinstance(c, dict) else dict(zip(_VAL_FIELDS, c))
+        for f in _VAL_FIELDS:
+            x = c.get(f)
+            setattr(r, f, x.ctypes.data if isinstance(x, np.ndarray) else _ptr(x))
+    return recs
+
+
+def values_device(plan: ValuePlan, cols, n: int, out, out_off, status=None, out_base: int = 0, cap: Optional[int] = None,
+                  stream=None):
+    """Device-resident batch (dg_vals_batch_device) over torch tensors or raw
+    device pointers. cols: one dict per column with the keys its kind reads,
+    in the shapes columns_device / column_list_device write: val int64[n] (a
+    scalar's value, a float64 column viewed as int64; str: the payload's
+    offset in src), len int32[n] and src uint8 (str; src with 16 spare bytes),
+    elem_off int64[n + 1] and elems int64 (lists and sets), present uint8[n]
+    (struct mode, optional). out uint8[cap + 16] or None to stop after the
+    offsets (sizing); out_off int64[n * K + 1]; status uint8[n * K] or None.
+    cap defaults to out's size less 16. What it fills is what
+    edit_many_device takes as val / val_off. Asynchronous on `stream`."""
+    s = _stream_handle(stream, out_off)
+    if cap is None:
+        cap = int(out.numel()) - 16 if hasattr(out, "numel") else 0
+    _lib.check(_lib.lib().dg_vals_batch_device(plan.ctx.h, plan.h, _val_cols(cols, plan.count), n, out_base, _ptr(out),
+                                               max(cap, 0), _ptr(out_off), _ptr(status), s))
+
+
+def _host_column(kind: int, column, n: int, present=None):
+    """a column of values_batch as the arrays dg_vals_batch_host reads"""
+    if len(column) != n:
+        raise ValueError("a column of %d values for %d messages" % (len(column), n))
+    c = {}
+    if kind & (VAL_LIST | VAL_SET):
+        off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(x) for x in column], out=off[1:])
+        dt = np.float64 if kind & 0x3F == VAL_F64 else None
+        rows = [np.asarray(x, dtype=dt) for x in column if len(x)]
+        flat = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+        c["elem_off"], c["elems"] = off, _as_u64(flat, kind & 0x3F)
+    elif kind == VAL_STR:
+        rows = [x.encode() if isinstance(x, str) else bytes(x) for x in column]
+        lens = np.fromiter((len(x) for x in rows), dtype=np.uint64, count=n)
+        c["val"] = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if n else np.zeros(0, dtype=np.uint64)
+        c["len"] = lens.astype(np.uint32)
+        c["src"] = np.frombuffer(b"".join(rows) + b"\0" * 16, dtype=np.uint8)
+    else:
+        c["val"] = _as_u64(np.asarray(column, dtype=np.float64 if kind == VAL_F64 else None), kind)
+    if present is not None:
+        c["present"] = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+        if len(c["present"]) != n:
+            raise ValueError("present of %d entries for %d messages" % (len(c["present"]), n))
+    return c
+
+
+def _as_u64(a: np.ndarray, elem: int) -> np.ndarray:
+    """the 64-bit inputs: floats as their bits (for a DOUBLE), integers mod 2^64"""
+    if a.dtype.kind == "f":
+        if elem != VAL_F64:
+            raise ValueError("a float array for an integer kind")
+        return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+    if a.dtype.kind == "b":
+        return a.astype(np.uint64)
+    if a.dtype.kind == "O":  # Python ints beyond int64
+        return np.array([int(x) & (2 ** 64 - 1) for x in a], dtype=np.uint64)
+    if a.dtype.kind not in "iu":
+        raise ValueError("a column of dtype %s" % a.dtype)
+    return np.ascontiguousarray(a.astype(np.int64) if a.dtype.kind == "i" else a.astype(np.uint64)).view(np.uint64)
+
+
+def _values_host(plan: ValuePlan, cols, n: int):
+    lib = _lib.lib()
+    k = plan.count
+    off = np.zeros(n * k + 1, dtype=np.uint64)
+    status = np.zeros(n * k, dtype=np.uint8)
+    need = C.c_uint64(0)
+    recs = _val_cols(cols, k)
+
+    for sized in (False, True):  # the first call sizes: the arena's bytes are known exactly after it
+        cap = int(need.value) if sized else 0
+        out = np.zeros(cap, dtype=np.uint8)
+        _lib.check(lib.dg_vals_batch_host(plan.ctx.h, plan.h, recs, n, out.ctypes.data if cap else None, cap,
+                                          off.ctypes.data, status.ctypes.data, C.byref(need)))
+        if not need.value:
+            break
+    return out, off, status
+
+
+def values_batch(columns, plan, ctx: Optional[Context] = None):
+    """The host path (dg_vals_batch_host): `plan` is a ValuePlan or a list of
+    kinds; per column a numpy integer or float array (a DOUBLE column: floats,
+    or integers taken as bits), a sequence of bytes / str (str columns), or a
+    sequence of sequences (lists and sets). Integers are taken mod 2^64 and
+    written at the kind's width. Returns (arena uint8, off uint64[n * K + 1],
+    status uint8[n * K]), message-major: item j of message i is
+    arena[off[i * K + j]:off[i * K + j + 1]]."""
+    vp = plan if isinstance(plan, ValuePlan) else ValuePlan(plan, None, ctx)
+    with _unless_given(vp, plan):
+        if len(columns) != vp.count:
+            raise ValueError("%d columns for a plan of %d" % (len(columns), vp.count))
+        n = len(columns[0])
+        return _values_host(vp, [_host_column(k, c, n) for k, c in zip(vp.kinds, columns)], n)
+
+
+def set_columns_batch(msgs: Sequence[bytes], parent, columns, desc=None, root_type: int = STRUCT,
+                      ctx: Optional[Context] = None) -> List[EditManyResult]:
+    """SetMany from columns: below the node at `parent`, every (step, kind,
+    column) sets the child at `step` of message i to column[i] encoded as
+    `kind` (values_batch, then set_many_batch's host entry with the kinds'
+    wire types). At most EDITM_MAX_ITEMS columns."""
+    columns = list(columns)
+    if not 1 <= len(columns) <= EDITM_MAX_ITEMS:
+        raise ValueError("%d columns (1 to %d)" % (len(columns), EDITM_MAX_ITEMS))
+    with ValuePlan([c[1] for c in columns], None, ctx) as vp:
+        if any(len(c[2]) != len(msgs) for c in columns):
+            raise ValueError("a column's length is not the batch's")
+        arena, off, _ = values_batch([c[2] for c in columns], vp) if msgs else (np.zeros(0, np.uint8), np.zeros(1, np.uint64), None)
+        with EditManyPlan(parent, [c[0] for c in columns], EDIT_SET, desc, ctx) as plan:
+            return _editm_batch(msgs, plan, None, vp.wire_types, root_type, encoded=(arena, off))
+
+
+def build_structs_batch(fields, ctx: Optional[Context] = None) -> List[bytes]:
+    """NewNodeStruct for a batch: `fields` is a list of (field_id, kind,
+    column[, present]); message i holds, in the order given, every field whose
+    present[i] is true (all, without present), then STOP."""
+    fields = [tuple(f) for f in fields]
+    n = len(fields[0][2])
+    with ValuePlan([f[1] for f in fields], [f[0] for f in fields], ctx) as vp:
+        cols = [_host_column(k, f[2], n, f[3] if len(f) > 3 else None) for k, f in zip(vp.kinds, fields)]
+        arena, off, _ = _values_host(vp, cols, n)
+        return _split(arena, off[::vp.count])

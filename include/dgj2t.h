@@ -92,6 +92,8 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *                                 (tools/kids_bench.py times the count pass alone with it, without d_recs)
  *   "cols_full_search" (no env)   timing only: 1 = every lane of dg_cols_list_device's emit searches all n offsets
  *                                 for its message (0: between the answers of its block's first and last lane)
+ *   "vals_lane_emit" (no env)     1 = dg_vals_* writes every cell, string payloads and list elements included, by the
+ *                                 one lane that owns it (0: a head pass and a wave-parallel body pass)
  *   "edit_reuse_rec" (no env)     timing only: 1 = a dg_edit_* or dg_editm_* launch of as many messages and items as
  *                                 the context's previous one skips the lookup and splices from its records
  *                                 (tools/edit_bench.py times the splice alone with it; another batch or other
@@ -946,6 +948,86 @@ int dg_cols_list_device(dg_ctx *ctx, const dg_cols *cols, uint32_t k, const uint
 int dg_cols_batch_host(dg_ctx *ctx, const dg_cols *cols, uint8_t root_type, const uint8_t *thrift,
                        const uint64_t *in_off, uint64_t n, uint64_t *val, dg_col_cell *cell, uint32_t *len,
                        uint64_t *elem_off, uint64_t *elems, uint64_t elem_cap, uint64_t *need);
+
+/* ------------------------------------------------------------------------
+ * vals: typed column writes, the inverse of cols: tensors encoded to
+ * Thrift-binary values (the reference's NewNodeBool ... NewNodeString /
+ * NewNodeBinary / NewNodeList / NewNodeSet, thrift/generic/node.go:92-201, over
+ * WriteAny, thrift/binary.go:1480-1682, and BinaryEncoding.Encode*,
+ * binary.go:2101-2149) or, with field ids, to whole struct messages
+ * (NewNodeStruct). A plan holds K columns, 1 <= K <= DG_VALS_MAX_COLS, each
+ * with a kind (dgj2t_defs.h DG_VAL_*); a batch has n * K < 2^32 cells.
+ * dg_vals_create answers DG_E_ARG with a text naming the kind and the column
+ * for any other kind, and for another K.
+ *
+ * What cell (i, k) writes, from column k's dg_val_col at row i:
+ *   BOOL               one byte, 1 if the 64-bit input is non-zero, else 0
+ *                      (EncodeBool).
+ *   I08 I16 I32 I64    the low 8 / 16 / 32 / 64 bits of the input, big-endian:
+ *                      Go's int16(x) conversion. Nothing is range-checked and
+ *                      nothing is an error, so what DG_COL_INT read from a
+ *                      field of a width and what is written at that width are
+ *                      the same bytes (an I08 read as 0..255 writes its low
+ *                      byte).
+ *   DOUBLE             the 8 input bytes swapped and nothing else (NaN
+ *                      payloads, the signalling bit, -0.0 and denormals
+ *                      survive as bits, as DG_COL_F64 reads them).
+ *   STRING             the i32 big-endian length d_len[i], then the d_len[i]
+ *                      bytes at d_src + d_val[i] (EncodeString / EncodeBinary).
+ *   LIST / SET         the element type byte, the i32 big-endian count
+ *                      d_elem_off[i + 1] - d_elem_off[i], then the elements
+ *                      d_elems[d_elem_off[i] ...] encoded as the scalars above.
+ *                      Count 0 is legal: the kind names the element type
+ *                      (WriteAny refuses an empty []interface{}).
+ * Lists of strings, structs or containers, maps, and descriptor-aware writes
+ * (WriteAnyWithDesc) are not part of this.
+ *
+ * Cell errors: a STRING length or a list count above 2^31 - 1, or an item
+ * (the value and, in struct mode, its field header and STOP) of 2^32 bytes or
+ * more, is DG_VAL_E_SIZE: the cell is flagged in d_status and written as the
+ * empty value of its kind (00 00 00 00; elem 00 00 00 00), so the arena always
+ * holds well-formed Thrift. Every other cell is DG_VAL_OK.
+ *
+ * Struct mode (field_ids given, K of them): item j of a message is preceded by
+ * EncodeFieldBegin(wire type, field_ids[j]), 3 bytes, and the last item of
+ * every message is followed by the STOP byte, so message i is
+ * d_out[d_out_off[i * K], d_out_off[(i + 1) * K]). Fields go in column order
+ * (Go's map order is unspecified). d_present[i] == 0 leaves column k's field
+ * out of message i; a message with no field present is the STOP byte alone.
+ * Without field ids a d_present pointer is DG_E_ARG at the call.
+ */
+typedef struct dg_vals dg_vals;
+int dg_vals_create(dg_ctx *ctx, const uint8_t *kinds, uint32_t K, const int16_t *field_ids, dg_vals **out);
+void dg_vals_destroy(dg_vals *p);
+uint32_t dg_vals_count(const dg_vals *p);
+/* the wire type of column k's values (dg_editm_batch_device's val_types[k]):
+ * the kind itself for a scalar, 15 for a list, 14 for a set; 0 for no such column */
+uint8_t dg_vals_wire_type(const dg_vals *p, uint32_t k);
+
+/* Device buffers, stream-ordered, async (stream NULL: the context's). cols: K
+ * records in HOST memory whose pointers are device pointers. The outputs are
+ * a message-major arena, dg_editm_batch_device's d_val / d_val_off: d_out_off
+ * (u64, n * K + 1 entries, 8-byte aligned), [i * K + j] the start of item j of
+ * message i, [0] = out_base, the last entry the arena's end; d_out the bytes,
+ * cap + 16 allocated, nothing stored at an index >= cap and the 16 spare bytes
+ * untouched; d_status (u8, n * K, message-major) may be NULL. d_out NULL stops
+ * after the offsets and statuses (sizing). n = 0 returns DG_OK and launches
+ * nothing. Three steps: a size pass (a plan of scalars only, with no d_present,
+ * has closed-form offsets: no scan, and the same launch writes the bytes), the
+ * scan of the lengths (cols' scan; the lengths and the tile sums are the
+ * component's own, one set per context, ordered across streams like every
+ * shared workspace), and the emit: a head pass, one lane per cell, and a body
+ * pass in which whole waves store string payloads and list elements in
+ * contiguous runs. Knob "vals_lane_emit" = 1: one lane per cell writes all of
+ * it (the baseline the measurements compare with). */
+int dg_vals_batch_device(dg_ctx *ctx, const dg_vals *plan, const dg_val_col *cols, uint64_t n, uint64_t out_base,
+                         uint8_t *d_out, uint64_t cap, uint64_t *d_out_off, uint8_t *d_status, void *stream);
+/* Host buffers, synchronous (no spare bytes needed): cols' pointers are host
+ * pointers, out_off (n * K + 1, never NULL) starts at 0, status may be NULL.
+ * *need = the arena's bytes. out NULL with cap 0 stops there (sizing);
+ * otherwise DG_E_NOMEM when cap < *need. */
+int dg_vals_batch_host(dg_ctx *ctx, const dg_vals *plan, const dg_val_col *cols, uint64_t n, uint8_t *out, uint64_t cap,
+                       uint64_t *out_off, uint8_t *status, uint64_t *need);
 
 /* Timing helper for benchmarks: launch the device batch `iters` times on the
  * context stream bracketed by HIP events; returns total milliseconds of GPU

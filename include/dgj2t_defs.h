@@ -310,6 +310,31 @@ typedef struct dg_col_cell {
     uint32_t aux;   /* dg_tget_rec's aux; a list whose element type the cast rejects: that element type */
 } dg_col_cell; /* 8 bytes */
 
+/* vals (typed column writes, include/dgj2t.h dg_vals_*): a column's kind names
+ * the wire encoding to write: a scalar kind is the Thrift wire type itself (2
+ * BOOL, 3 I08, 4 DOUBLE, 6 I16, 8 I32, 10 I64, 11 STRING); DG_VAL_LIST | elem
+ * and DG_VAL_SET | elem, elem one of 2, 3, 4, 6, 8, 10, are the container kinds.
+ * A cell's status is DG_VAL_OK or DG_VAL_E_SIZE. */
+#define DG_VALS_MAX_COLS 16u
+#define DG_VAL_LIST 0x40u
+#define DG_VAL_SET 0x80u
+#define DG_VAL_OK 0u
+#define DG_VAL_E_SIZE 1u /* a STRING length or a list count above 2^31 - 1, or an item of 2^32 bytes or more: the
+                            cell is written as the empty value of its kind */
+/* one column's inputs, in the shapes dg_cols_* writes (device pointers at the
+ * device entry, host pointers at the host entry); what a kind does not read
+ * may be NULL, and so may d_src and d_elems of a column whose strings or lists
+ * are all empty */
+typedef struct dg_val_col {
+    const uint64_t *d_val;      /* n: a scalar's value (DOUBLE: its bits); STRING: the payload's byte offset in d_src */
+    const uint32_t *d_len;      /* n: STRING: the payload's length */
+    const uint8_t *d_src;       /* STRING: the arena the offsets point into, 16 readable bytes after its last payload
+                                   byte */
+    const uint64_t *d_elem_off; /* n + 1: lists and sets: dg_cols_list_device's d_elem_off */
+    const uint64_t *d_elems;    /* lists and sets: its d_elems, 8 bytes an element */
+    const uint8_t *d_present;   /* n or NULL (all present); struct mode only: 0 leaves the field out of the message */
+} dg_val_col;
+
 /* t2j (Thrift binary -> JSON, conv/t2j) option bits: the conv.Options fields
  * conv/t2j/impl.go reads (conv/api.go:52-121) */
 #define DG_T2J_BYTE_AS_UINT8 (1ull << 0)     /* ByteAsUint8 */
