@@ -195,8 +195,6 @@ DGI uint64_t eqbytes(uint64_t w, uint8_t c)
     const uint32_t cc = (uint32_t)c * 0x01010101u;
     return (uint64_t)zb32((uint32_t)w ^ cc) | ((uint64_t)zb32((uint32_t)(w >> 32) ^ cc) << 32);
 }
-/* 0xFF in every byte whose top bit is set in m (m: 0x80 flags only) */
-DGI uint32_t ff32(uint32_t m) { return (m << 1) - (m >> 7); }
 
 /* Thrift output with a hard slot bound and 8-byte write combining.
  * Bytes are assembled in `wbuf` (the word holding position len) and stored

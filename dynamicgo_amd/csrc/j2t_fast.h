@@ -544,26 +544,41 @@ DGI bool fast_string(S &src, SI &p, Out &out)
     return true;
 }
 
-/* 8 base64 characters -> 6 bytes (little-endian in *o); false if any is not
- * in the standard alphabet */
+/* byte k of the result = byte sel.k (0..7) of the 8-byte table hi:lo (v_perm_b32) */
+DGI uint32_t perm8(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t t = (uint64_t)hi << 32 | lo;
+    uint32_t r = 0;
+    for (uint32_t k = 0; k < 4; k++) r |= (uint32_t)((t >> 8 * ((sel >> 8 * k) & 7)) & 0xFF) << 8 * k;
+    return r;
+#endif
+}
+
 /* 4 base64 characters (little-endian in w) -> 3 bytes in output order in the
- * low 24 bits of o; false if any is not in the standard alphabet */
+ * low 24 bits of o; false if any is not in the standard alphabet.
+ * A character's high nibble names its class -- 2: '+' '/', 3: digits, 4 5:
+ * upper case, 6 7: lower case -- and '/' is moved to index 1; three table
+ * lookups by those indices give each byte its class's lower bound, upper
+ * bound and offset to the 6-bit value. */
 DGI bool b64_4(uint32_t w, uint32_t &o)
 {
     const uint32_t H = 0x80808080u;
-    if (w & H) return false;
-#define DG_GE(lo) ((w + (uint32_t)(0x80 - (lo)) * 0x01010101u) & H)
-    const uint32_t up = DG_GE('A') & ~DG_GE('Z' + 1);
-    const uint32_t lw = DG_GE('a') & ~DG_GE('z' + 1);
-    const uint32_t dg = DG_GE('0') & ~DG_GE('9' + 1);
-#undef DG_GE
-    const uint32_t pl = zb32(w ^ 0x2B2B2B2Bu), sl = zb32(w ^ 0x2F2F2F2Fu);
-    if ((up | lw | dg | pl | sl) != H) return false;
-    /* per-byte offsets: 'A'->0 (-65), 'a'->26 (-71), '0'->52 (+4), '+'->62 (+19), '/'->63 (+16) */
-    const uint32_t off = (ff32(up) & 0xBFBFBFBFu) | (ff32(lw) & 0xB9B9B9B9u) | (ff32(dg) & 0x04040404u) |
-                         (ff32(pl) & 0x13131313u) | (ff32(sl) & 0x10101010u);
-    const uint32_t v = ((w & 0x7F7F7F7Fu) + (off & 0x7F7F7F7Fu)) ^ ((w ^ off) & H); /* bytewise add mod 256 */
-    const uint32_t t = ((v & 0x3Fu) << 18) | (((v >> 8) & 0x3Fu) << 12) | (((v >> 16) & 0x3Fu) << 6) | (v >> 24);
+    const uint32_t sl = ~w & H & ~(((w | H) ^ 0x2F2F2F2Fu) + 0xFEFEFEFFu); /* 0x80 where '/' */
+    const uint32_t idx = ((w >> 4) & 0x07070707u) - (sl >> 7);
+    const uint32_t lo = perm8(0x70615041u, 0x302B2F7Fu, idx); /* 0: none 1: '/' 2: '+' 3: '0' 4: 'A' 5: 'P' 6: 'a' 7: 'p' */
+    const uint32_t hi = perm8(0xFAEFDACFu, 0xB9ABAF80u, idx); /* upper bounds | 0x80: '/' '+' '9' 'O' 'Z' 'o' 'z' */
+    const uint32_t of = perm8(0x39393F3Fu, 0x04131000u, idx); /* +16 +19 +4 -65 -65 -71 -71, mod 64 */
+    /* bit 7 per byte: lo <= c <= hi and c < 0x80. Each minuend byte has bit
+     * 7 set and lo's bytes have not, nor has a byte of w that can pass: a
+     * borrow between bytes comes only from a byte >= 0x80, which fails */
+    const uint32_t ok = ((w | H) - lo) & (hi - w) & ~w;
+    if ((ok & H) != H) return false;
+    const uint32_t v = (w + of) & 0x3F3F3F3Fu; /* c + of < 256: no carry between bytes */
+    const uint32_t ab = ((v & 0x003F003Fu) << 6) | ((v >> 8) & 0x003F003Fu);
+    const uint32_t t = ((ab & 0xFFFu) << 12) | (ab >> 16);
     o = (t >> 16) | (t & 0xFF00u) | ((t & 0xFFu) << 16);
     return true;
 }

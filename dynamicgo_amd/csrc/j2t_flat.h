@@ -39,6 +39,7 @@
  * kernel's list as in the small kernel.
  */
 #pragma once
+#include "fl_classify.h"
 #include "flat_image.h"
 #include "j2t_small.h"
 
@@ -136,9 +137,6 @@ DGI uint32_t g4_next(uint32_t v, uint32_t g)
     const uint32_t t = DG_DPP(v, 0x101); /* row_shl:1 */
     return g < 3 ? t : 0u;
 }
-
-/* 0x80 in each byte of w (32-bit half) equal to c */
-DGI uint32_t eq32(uint32_t w, uint32_t cc) { return zb32(w ^ cc); }
 
 /* The staged message in LDS, the SrcT interface without SrcT's one-word
  * cache: every access is its own LDS read, so independent reads overlap
@@ -978,30 +976,10 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(D
             const uint32_t lo_ = hi4 ? d[i + 1] : d[i], hi_ = hi4 ? d[i + 2] : d[i + 1];
             x[i] = __builtin_amdgcn_alignbyte(hi_, lo_, sh);
         }
-        /* 0x80-per-byte flags of two dwords -> 8 bits (byte i of the pair at bit i) */
-        auto pack8 = [](uint32_t m0, uint32_t m1_) -> uint32_t {
-            return (((m0 >> 7) | (m1_ >> 3)) * 0x01020408u) >> 24;
-        };
-        uint32_t ql = 0, qh = 0, cl = 0, ch = 0, kl = 0, kh = 0, anybs = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 8; j++) {
-            const uint32_t x0 = x[2 * j], x1 = x[2 * j + 1];
-            const uint32_t q8 = pack8(eq32(x0, 0x22222222u), eq32(x1, 0x22222222u));
-            const uint32_t c8 = pack8(eq32(x0, 0x2C2C2C2Cu), eq32(x1, 0x2C2C2C2Cu));
-            const uint32_t k8 = pack8(eq32(x0, 0x3A3A3A3Au), eq32(x1, 0x3A3A3A3Au));
-            anybs |= eq32(x0, 0x5C5C5C5Cu) | eq32(x1, 0x5C5C5C5Cu);
-            if (j < 4) {
-                ql |= q8 << (8 * j);
-                cl |= c8 << (8 * j);
-                kl |= k8 << (8 * j);
-            } else {
-                qh |= q8 << (8 * (j - 4));
-                ch |= c8 << (8 * (j - 4));
-                kh |= k8 << (8 * (j - 4));
-            }
-        }
-        uint64_t Q = ((uint64_t)qh << 32 | ql) & vmask, C = ((uint64_t)ch << 32 | cl) & vmask,
-                 K = ((uint64_t)kh << 32 | kl) & vmask;
+        /* two instructions per class and dword, packed by dot products (fl_classify.h) */
+        const FlMasks cm = fl_classify<false>(x);
+        const uint32_t anybs = cm.anybs;
+        uint64_t Q = cm.Q & vmask, C = cm.C & vmask, K = cm.K & vmask;
         const uint32_t nq = (uint32_t)__builtin_popcountll(Q);
         const uint32_t qx = g4_incl_sum(nq, g) - nq; /* quotes in the lanes before */
         /* in-string bytes: inclusive prefix XOR of the quotes (opening quote
@@ -1026,14 +1004,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) __attribute__((amdgpu_waves_per_eu(D
         if (hasbs) {
             /* a backslash before '"' or '\\' (an escaped quote or backslash) -> decline,
              * so every quote is a delimiter */
-            uint32_t bl = 0, bh = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) {
-                const uint32_t b8 = pack8(eq32(x[2 * j], 0x5C5C5C5Cu), eq32(x[2 * j + 1], 0x5C5C5C5Cu));
-                if (j < 4) bl |= b8 << (8 * j);
-                else bh |= b8 << (8 * (j - 4));
-            }
-            const uint64_t B = ((uint64_t)bh << 32 | bl) & vmask, QB = Q | B;
+            const uint64_t B = fl_classify<true>(x).B & vmask, QB = Q | B;
             const uint32_t nxt = g4_next((uint32_t)(QB & 1), g); /* the next lane's first byte */
             const uint64_t bb = B & ((QB >> 1) | ((uint64_t)nxt << 63));
             /* decode this lane's escapes into the message's table (an escape
