@@ -30,6 +30,8 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_kids_batch_device", "dg_kids_batch_host",
            "dg_cols_create", "dg_cols_destroy", "dg_cols_count", "dg_cols_batch_device", "dg_cols_list_device",
            "dg_cols_batch_host",
+           "dg_ents_create", "dg_ents_destroy", "dg_ents_count", "dg_ents_batch_device", "dg_ents_emit_device",
+           "dg_ents_batch_host",
            "dg_vals_create", "dg_vals_destroy", "dg_vals_count", "dg_vals_wire_type", "dg_vals_batch_device",
            "dg_vals_batch_host"]
 
@@ -141,6 +143,12 @@ def lib() -> C.CDLL:
         "dg_cols_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, u64]),
         "dg_cols_list_device": (i32, [vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
         "dg_cols_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, u64, P64]),
+        "dg_ents_create": (i32, [vp, C.c_char_p, sz, C.c_char_p, u32, C.POINTER(vp)]),
+        "dg_ents_destroy": (None, [vp]),
+        "dg_ents_count": (u32, [vp]),
+        "dg_ents_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, u64]),
+        "dg_ents_emit_device": (i32, [vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "dg_ents_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u64, P64]),
         "dg_vals_create": (i32, [vp, C.c_char_p, u32, vp, C.POINTER(vp)]),
         "dg_vals_destroy": (None, [vp]),
         "dg_vals_count": (u32, [vp]),

@@ -5,7 +5,7 @@
  * per-stream scratch records, the entry guard, the argument records of one
  * batch, the host batch of the thrift/generic and t2j entries (HostBatch) and the
  * error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host, editm_host, kids_host, cols_host, vals_host and j2t_pipe
+ * tget_host, cut_host, editm_host, kids_host, cols_host, ents_host, vals_host and j2t_pipe
  * use them).
  */
 #pragma once
@@ -279,6 +279,7 @@ struct Knobs {
     int64_t kids_wide_min = 256;  /* kids: a list, set or map node of fixed-size entries with at least this many children is emitted by the record-parallel kernel (0: never); emit pass, 16 384 x list<i64> of 64 / 128 / 256 / 1024, lane route 0.107 / 0.159 / 0.261 / 1.314 ms, wide route 0.264 / 0.270 / 0.278 / 0.350 */
     int64_t kids_no_scan = 0;     /* kids, timing only: 1 = a call leaves the scan out (rec_off is not written) */
     int64_t cols_full_search = 0; /* cols, timing only: 1 = every lane of the list emit searches all n offsets (0: between the answers of its block's first and last lane) */
+    int64_t ents_stage = 16;      /* ents: entries a lane of the variable-stride emit stages in LDS a round before the wave writes them out in runs, 4, 8 or 16 (anything else: 0 = every lane stores its entries itself); emit call (scan + emit) at 0 / 4 / 8 / 16, 16 384 x list<string> of 64 strings of 8 bytes: 0.127 / 0.126 / 0.116 / 0.114 ms, x map<string, i64> of 64 with keys of 64 bytes: 0.167 / 0.154 / 0.152 / 0.151; of 4 and 16 entries all four within 3 % */
     int64_t vals_lane_emit = 0;   /* vals: 1 = one lane per cell writes all of it, payload and elements included (0: the head pass and the wave-parallel body pass); call at 0 / 1, 16 384 x one string of 64 / 1 024 / 16 384 bytes: 0.128 / 0.139 / 0.440 against 0.095 / 0.141 / 0.882 ms, x list<double> of 64 / 256 / 1 024: 0.138 / 0.163 / 0.240 against 0.125 / 0.229 / 0.660 */
 };
 
@@ -347,6 +348,13 @@ struct dg_ctx {
     StreamOrder vals;
     DevArr<uint32_t> vals_len;
     DevArr<uint64_t> vals_sums;
+    /* ents (ents_host.hip): the cell pass's deep frames (32 MB, allocated by the
+     * first call), its queue, two alternating queue counters and the scan's
+     * tile sums: its own, like cols' */
+    SharedWs ents;
+    DevArr<uint32_t> ents_list, ents_cnt_buf;
+    AltCounters ents_cnt;
+    DevArr<uint64_t> ents_sums;
     /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB) */
     SharedWs t2j_tok;
     /* t2j deep pass: T2J_DEEP_DEPTH frames per lane (about 100 MB, allocated
@@ -423,6 +431,14 @@ struct dg_path {
 
 /* a column plan on its context's device (cols_host.hip): a path set and one kind per path */
 struct dg_cols {
+    dg_ctx *ctx;
+    DevArr<uint8_t> d_blob;
+    dg_path_hdr hdr;
+    uint8_t kinds[DG_TGET_MAX_PATHS];
+};
+
+/* an entry-column plan (ents_host.hip): a path set and one DG_ENT_* kind per path */
+struct dg_ents {
     dg_ctx *ctx;
     DevArr<uint8_t> d_blob;
     dg_path_hdr hdr;

@@ -125,6 +125,7 @@ static int64_t *knob_ref(dg_ctx *c, const char *name)
     if (!strcmp(name, "kids_wide_min")) return &K.kids_wide_min;
     if (!strcmp(name, "kids_no_scan")) return &K.kids_no_scan;
     if (!strcmp(name, "cols_full_search")) return &K.cols_full_search;
+    if (!strcmp(name, "ents_stage")) return &K.ents_stage;
     if (!strcmp(name, "vals_lane_emit")) return &K.vals_lane_emit;
     return nullptr;
 }

@@ -1,7 +1,10 @@
 """thrift/generic on the GPU. Typed column writes (the last part of this
 module: ValuePlan, values_batch, values_device, set_columns_batch,
-build_structs_batch: the NewNode* constructors over tensors), typed column
-reads (the part before it: ColumnPlan, columns_batch, columns_device, column_list_device:
+build_structs_batch: the NewNode* constructors over tensors), entry columns
+(the part before it: EntryPlan, entries_batch, entries_device,
+entry_emit_device: GetByPath followed by Node.List of strings / StrMap / IntMap
+as ragged tensors), typed column
+reads (the part before that: ColumnPlan, columns_batch, columns_device, column_list_device:
 GetByPath followed by Node.Int / Float64 / String / List ... as tensors),
 batched SetMany (EditManyPlan, set_many_batch,
 unset_many_batch, edit_many_device: several children of one node edited in one
@@ -1117,6 +1120,163 @@ def columns_batch(msgs: Sequence[bytes], columns, desc=None, root_type: int = ST
                 c.values = val[k].view(np.float64)
             else:
                 c.values = val[k].view(np.int64)
+            out.append(c)
+        return out
+
+
+# ---------------------------------------------------------------------------
+# Entry columns: GetByPath followed by Node.List with String per element,
+# Node.StrMap or Node.IntMap for every message of a batch, as ragged columns
+# (thrift/generic/cast.go:198-286; dg_ents_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+ENT_BOOL, ENT_INT, ENT_F64, ENT_STR = 1, 3, 4, 5  # DG_ENT_*: the value kinds
+ENT_LISTSTR, ENT_STRMAP, ENT_INTMAP = 0x15, 0x20, 0x40
+_ENT_VALS = {"bool": ENT_BOOL, "int": ENT_INT, "float64": ENT_F64, "f64": ENT_F64, "str": ENT_STR}
+_ENT_KINDS = {"list[str]": ENT_LISTSTR}
+_ENT_KINDS.update({"%s[%s]" % (m, v): c | k for m, c in (("strmap", ENT_STRMAP), ("intmap", ENT_INTMAP))
+                   for v, k in _ENT_VALS.items()})
+
+
+def ent_kind(kind) -> int:
+    """A kind as DG_ENT_* or by name: list[str], strmap[v] and intmap[v] with v one of bool, int, float64 (f64), str."""
+    k = _ENT_KINDS.get(kind, kind)
+    if k not in _ENT_KINDS.values():
+        raise ValueError("unknown entry kind %r" % (kind,))
+    return int(k)
+
+
+class EntryPlan(_Handle):
+    """1 to 8 entry columns, each a path (a list of Path steps; PathFieldName
+    is resolved through `desc`) and a kind (ent_kind), on one context's device
+    (dg_ents). `columns` is a list of (path, kind)."""
+    _destroy = "dg_ents_destroy"
+
+    def __init__(self, columns, desc=None, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.kinds = [ent_kind(k) for _, k in columns]
+        self.blob = compile_paths([p for p, _ in columns], desc)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dg_ents_create(self.ctx.h, self.blob, len(self.blob), bytes(self.kinds), len(self.kinds),
+                                             C.byref(h)))
+        self.h = h
+        self.count = int(_lib.lib().dg_ents_count(h))
+
+
+def entries_device(plan: EntryPlan, thrift, in_off, n: int, val, cell, lens, spans, root_type: int = STRUCT,
+                   stream=None, max_len: int = 0):
+    """The cell pass (dg_ents_batch_device) over torch tensors or raw device
+    pointers: thrift uint8[>= in_off[n] + 16]; in_off int64[n + 1]; val
+    int64[P, n]; cell P * n 8-byte cells (e.g. int32 of shape (P, n, 2)); lens
+    and spans int32[P, n]. Column-major: a column is one contiguous tensor.
+    Asynchronous on `stream` (a torch stream, a raw stream handle, or None for
+    torch's current stream when `thrift` is a tensor)."""
+    s = _stream_handle(stream, thrift)
+    _lib.check(_lib.lib().dg_ents_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n, _ptr(val),
+                                               _ptr(cell), _ptr(lens), _ptr(spans), s, max_len))
+
+
+def entry_emit_device(plan: EntryPlan, k: int, thrift, n: int, val_k, cell_k, len_k, span_k, ent_off, keys=None,
+                      key_lens=None, vals=None, val_lens=None, ent_cap: int = 0, stream=None):
+    """Column k's entries (dg_ents_emit_device) behind entries_device on the
+    same stream: val_k / cell_k / len_k / span_k are column k's rows of its
+    outputs; ent_off int64[n + 1] receives the scanned counts ([n] = the
+    total); keys and vals int64[ent_cap] (float64 values:
+    .view(torch.float64)), key_lens and val_lens int32[ent_cap]; any of the
+    four may be None, all four None stops after the scan."""
+    s = _stream_handle(stream, thrift)
+    _lib.check(_lib.lib().dg_ents_emit_device(plan.ctx.h, plan.h, k, _ptr(thrift), n, _ptr(val_k), _ptr(cell_k),
+                                              _ptr(len_k), _ptr(span_k), _ptr(ent_off), _ptr(keys), _ptr(key_lens),
+                                              _ptr(vals), _ptr(val_lens), ent_cap, s))
+
+
+class EntryColumn:
+    """One column of entries_batch: .kind; .status (uint8[n]: OK, NOT_FOUND,
+    E_READ, E_TYPE or COL_E_UNSUPPORTED), .valid, .type, .step, .aux (the
+    cell's other fields; a map cell's aux: key type | value type << 8),
+    .error(i), .offsets (int64[n + 1]: message i's entries are
+    [offsets[i], offsets[i + 1])) and .lengths (the counts). .keys[i] and
+    .values[i] are message i's keys and values in wire order, duplicates kept:
+    ints, bools, floats or bytes by kind; .keys is None for list[str].
+    .items(i) pairs them."""
+    __slots__ = ("kind", "status", "valid", "type", "step", "aux", "offsets", "lengths", "keys", "values")
+
+    def error(self, i: int):
+        return COL_ERROR_NAMES.get(int(self.status[i]), "ErrRead")
+
+    def items(self, i: int):
+        return list(zip(self.keys[i], self.values[i])) if self.keys is not None else list(self.values[i])
+
+    def __repr__(self):
+        return "EntryColumn(kind=%#x, %d cells, %d valid)" % (self.kind, len(self.status), int(self.valid.sum()))
+
+
+def entries_records(msgs: Sequence[bytes], plan: EntryPlan, root_type: int = STRUCT):
+    """The raw outputs of dg_ents_batch_host: (val uint64[P, n], cell
+    COL_CELL_DTYPE[P, n], lens uint32[P, n], ent_off uint64[P, n + 1], keys
+    uint64[all], key_lens uint32[all], vals uint64[all], val_lens uint32[all],
+    arena); string keys, values and elements are offsets into `arena`, the
+    messages back to back."""
+    n, P = len(msgs), plan.count
+    lib = _lib.lib()
+    val = np.zeros((P, n), dtype=np.uint64)
+    cell = np.zeros((P, n), dtype=COL_CELL_DTYPE)
+    lens = np.zeros((P, n), dtype=np.uint32)
+    ent_off = np.zeros((P, n + 1), dtype=np.uint64)
+    need = C.c_uint64(0)
+    if n == 0:
+        _lib.check(lib.dg_ents_batch_host(plan.ctx.h, plan.h, root_type, None, None, 0, None, None, None,
+                                          ent_off.ctypes.data, None, None, None, None, 0, C.byref(need)))
+        z8, z4 = np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint32)
+        return val, cell, lens, ent_off, z8, z4, z8.copy(), z4.copy(), np.zeros(16, dtype=np.uint8)
+    arena, in_off = _arena(msgs)
+
+    def call(cap):
+        out = (np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint64),
+               np.zeros(cap, dtype=np.uint32))
+        return lib.dg_ents_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
+                                      val.ctypes.data, cell.ctypes.data, lens.ctypes.data, ent_off.ctypes.data,
+                                      *(o.ctypes.data if cap else None for o in out), cap, C.byref(need)), out
+
+    # a guess the call corrects (an entry takes at least two bytes of its message, five as a rule)
+    out = _until_fits(call, int(in_off[n]) // 4 + 64, need)
+    return (val, cell, lens, ent_off) + tuple(o[:int(need.value)] for o in out) + (arena,)
+
+
+def entries_batch(msgs: Sequence[bytes], columns, desc=None, root_type: int = STRUCT,
+                  ctx: Optional[Context] = None) -> List[EntryColumn]:
+    """GetByPath and Node.List / StrMap / IntMap for every message of a batch
+    (dg_ents_batch_host): `columns` is a list of (path, kind) or an EntryPlan;
+    one EntryColumn comes back per path."""
+    plan = columns if isinstance(columns, EntryPlan) else EntryPlan(columns, desc, ctx)
+    with _unless_given(plan, columns):
+        n = len(msgs)
+        val, cell, lens, ent_off, keys, klens, vals, vlens, arena = entries_records(msgs, plan, root_type)
+        raw = arena.tobytes()
+
+        def decode(v, ls, is_str, vk):
+            if is_str:
+                return [raw[o:o + ln] for o, ln in zip(v.tolist(), ls.tolist())]
+            if vk == ENT_F64:
+                return v.view(np.float64).tolist()
+            if vk == ENT_BOOL:
+                return (v != 0).tolist()
+            return v.view(np.int64).tolist()
+
+        out = []
+        for k, kind in enumerate(plan.kinds):
+            c = EntryColumn()
+            c.kind, c.status, c.type, c.step, c.aux = kind, cell[k]["status"], cell[k]["type"], cell[k]["step"], cell[k]["aux"]
+            c.valid = c.status == OK
+            eo = ent_off[k].astype(np.int64)
+            a, b = int(eo[0]), int(eo[n])
+            c.offsets, c.lengths = eo - eo[0], lens[k]
+            cuts = c.offsets.tolist()
+            vs = decode(vals[a:b], vlens[a:b], kind == ENT_LISTSTR or kind & 15 == ENT_STR, kind & 15)
+            c.values = [vs[x:y] for x, y in zip(cuts, cuts[1:])]
+            c.keys = None
+            if kind != ENT_LISTSTR:
+                ks = decode(keys[a:b], klens[a:b], bool(kind & ENT_STRMAP), ENT_INT)
+                c.keys = [ks[x:y] for x, y in zip(cuts, cuts[1:])]
             out.append(c)
         return out
 

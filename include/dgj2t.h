@@ -92,6 +92,9 @@ int dg_ctx_counters(dg_ctx *ctx, uint64_t *out, int n, int reset);
  *                                 (tools/kids_bench.py times the count pass alone with it, without d_recs)
  *   "cols_full_search" (no env)   timing only: 1 = every lane of dg_cols_list_device's emit searches all n offsets
  *                                 for its message (0: between the answers of its block's first and last lane)
+ *   "ents_stage"  (no env)        dg_ents_emit_device's variable-stride emit: 4, 8 or 16 = a lane stages that many
+ *                                 entries in LDS a round and its wave writes them out in runs (16); 0, and anything
+ *                                 else: every lane stores its entries itself
  *   "vals_lane_emit" (no env)     1 = dg_vals_* writes every cell, string payloads and list elements included, by the
  *                                 one lane that owns it (0: a head pass and a wave-parallel body pass)
  *   "edit_reuse_rec" (no env)     timing only: 1 = a dg_edit_* or dg_editm_* launch of as many messages and items as
@@ -948,6 +951,104 @@ int dg_cols_list_device(dg_ctx *ctx, const dg_cols *cols, uint32_t k, const uint
 int dg_cols_batch_host(dg_ctx *ctx, const dg_cols *cols, uint8_t root_type, const uint8_t *thrift,
                        const uint64_t *in_off, uint64_t n, uint64_t *val, dg_col_cell *cell, uint32_t *len,
                        uint64_t *elem_off, uint64_t *elems, uint64_t elem_cap, uint64_t *need);
+
+/* ------------------------------------------------------------------------
+ * ents: entry columns, the containers cols leaves out: GetByPath followed by
+ * Node.List with String per element, Node.StrMap or Node.IntMap
+ * (thrift/generic/cast.go:198-286), for a whole batch, as ragged columns. A
+ * column is one path plus a kind (dgj2t_defs.h DG_ENT_*); a plan holds 1 to
+ * DG_TGET_MAX_PATHS columns; dg_ents_create takes dg_path_create's blob with
+ * its limits and texts and n_kinds kinds, one per path (DG_E_ARG with a text
+ * for an unknown kind or another count). A component beside cols: dg_cols_*
+ * takes none of these kinds.
+ *
+ * A cell is a value (8 bytes), a dg_col_cell, a length and a span:
+ *   the lookup fails   status DG_TGET_NOT_FOUND / E_READ / E_TYPE with the
+ *                      type, step and aux dg_tget_rec would hold; value 0.
+ *   the node is of another container class (LISTSTR: not LIST or SET; the map
+ *   kinds: not MAP)    DG_COL_E_UNSUPPORTED, type = the wire type found,
+ *                      step = the path length, aux 0.
+ *   DG_ENT_LISTSTR     the header as ReadListBegin reads it: an element type
+ *                      that is not Valid() is DG_TGET_E_READ (type 0, step =
+ *                      the path length) at any size. Size 0 with a valid
+ *                      element type: OK, length 0. Size > 0 and an element
+ *                      type other than STRING: E_UNSUPPORTED, aux = the
+ *                      element type. OK: type = the element type, value = the
+ *                      arena offset of element 0 (its length prefix).
+ *   DG_ENT_STRMAP | v  ReadMapBegin first: a key or value type that is not
+ *                      Valid() is DG_TGET_E_READ (type 0, aux 0) at any size.
+ *                      Then a key type other than STRING is E_UNSUPPORTED at
+ *                      any size, size 0 included.
+ *   DG_ENT_INTMAP | v  the key byte is tested BEFORE the header is read: a key
+ *                      byte that is not I08 / I16 / I32 / I64, valid or not, is
+ *                      E_UNSUPPORTED with aux = that byte alone (the value
+ *                      byte was not read). Then a value type that is not
+ *                      Valid() is DG_TGET_E_READ (type 0, aux 0).
+ *   both map kinds     every cell whose header was read carries it in aux:
+ *                      key type | value type << 8. Size 0: OK, length 0,
+ *                      whatever the value type. Size > 0 and a value type the
+ *                      value kind rejects (INT: anything but I08 / I16 / I32 /
+ *                      I64; F64: but DOUBLE; BOOL: but BOOL; STR: but STRING):
+ *                      E_UNSUPPORTED. OK: type = MAP, value = the arena offset
+ *                      of the first entry (its key).
+ * An OK cell's length is the count and its span the bytes from the value's
+ * offset to the container's end, which the lookup's final skip found: the
+ * emit's walk never reads an entry past it. Elsewhere value, length and span
+ * are 0. A body cut short or a negative count never reaches the cast: the
+ * lookup's skip has made it DG_TGET_E_READ. Entries come out in wire order
+ * with duplicate keys kept (a Go map keeps the last and has no order), and
+ * the value type is checked once, on the header.
+ */
+typedef struct dg_ents dg_ents;
+int dg_ents_create(dg_ctx *ctx, const void *path_blob, size_t len, const uint8_t *kinds, uint32_t n_kinds,
+                   dg_ents **out);
+void dg_ents_destroy(dg_ents *p);
+uint32_t dg_ents_count(const dg_ents *p);
+
+/* The cell pass: dg_cols_batch_device's contract (device buffers, stream-
+ * ordered, async, column-major outputs of P * n entries, the 16 readable bytes
+ * past the arena, n * P < 2^32, n = 0 launches nothing) with d_len required
+ * and d_span (u32, P * n) beside it. The deep pass's queue, counters and
+ * frames are the component's own. */
+int dg_ents_batch_device(dg_ctx *ctx, const dg_ents *ents, uint8_t root_type, const uint8_t *d_thrift,
+                         const uint64_t *d_in_off, uint64_t n, uint64_t *d_val, dg_col_cell *d_cell, uint32_t *d_len,
+                         uint32_t *d_span, void *stream, uint64_t max_len);
+/* Column k's entries after dg_ents_batch_device on the same stream (or ordered
+ * behind it): d_val_k / d_cell_k / d_len_k / d_span_k are column k's parts of
+ * its outputs (d_val + k * n, ...). A scan of the counts fills d_ent_off (u64,
+ * n + 1 entries, [n] = the total); message i owns the slots [d_ent_off[i],
+ * d_ent_off[i + 1]) of up to four arrays:
+ *   d_key (u64)      an int key as ReadInt reads it (I08 unsigned: 0xFF is
+ *                    255; I16 / I32 / I64 sign-extended); a string key: the
+ *                    arena offset of its payload. Not written by LISTSTR.
+ *   d_key_len (u32)  string keys: the payload's length. Written by the STRMAP
+ *                    kinds alone.
+ *   d_val (u64)      the value as the cols cell of its kind decodes it (BOOL:
+ *                    1 if the byte is exactly 1; INT: I08 unsigned, the rest
+ *                    sign-extended; F64: bit for bit); a string value or a
+ *                    LISTSTR element: the arena offset of its payload.
+ *   d_val_len (u32)  string values and elements: the payload's length.
+ *                    Written by LISTSTR and the STR value kinds alone.
+ * The (offset, length) pairs are the ones dg_pack_device_scan takes. An array
+ * the caller does not need may be NULL; all four NULL stops after the scan
+ * (sizing). No slot at an index >= ent_cap is stored; empty and failed cells
+ * contribute nothing. DG_E_ARG when k names no column. */
+int dg_ents_emit_device(dg_ctx *ctx, const dg_ents *ents, uint32_t k, const uint8_t *d_thrift, uint64_t n,
+                        const uint64_t *d_val_k, const dg_col_cell *d_cell_k, const uint32_t *d_len_k,
+                        const uint32_t *d_span_k, uint64_t *d_ent_off, uint64_t *d_key, uint32_t *d_key_len,
+                        uint64_t *d_val, uint32_t *d_val_len, uint64_t ent_cap, void *stream);
+/* Host buffers, synchronous (no spare bytes needed): val, cell and len (P * n
+ * each, never NULL when n > 0) as above, offsets relative to `thrift`. ent_off
+ * has P * (n + 1) entries, column k's at [k * (n + 1), ...): its message i owns
+ * the slots [ent_off[i], ent_off[i + 1]) of key / key_len / ent_val /
+ * ent_val_len, the columns' entries one after the other, and *need = the last
+ * entry = all entries. The four arrays NULL with ent_cap 0 stops there
+ * (sizing); otherwise DG_E_NOMEM when ent_cap < *need, and an array that is
+ * NULL is not filled. Slots of an array a column's kind does not write hold 0. */
+int dg_ents_batch_host(dg_ctx *ctx, const dg_ents *ents, uint8_t root_type, const uint8_t *thrift,
+                       const uint64_t *in_off, uint64_t n, uint64_t *val, dg_col_cell *cell, uint32_t *len,
+                       uint64_t *ent_off, uint64_t *key, uint32_t *key_len, uint64_t *ent_val, uint32_t *ent_val_len,
+                       uint64_t ent_cap, uint64_t *need);
 
 /* ------------------------------------------------------------------------
  * vals: typed column writes, the inverse of cols: tensors encoded to

@@ -310,6 +310,21 @@ typedef struct dg_col_cell {
     uint32_t aux;   /* dg_tget_rec's aux; a list whose element type the cast rejects: that element type */
 } dg_col_cell; /* 8 bytes */
 
+/* ents (entry columns, include/dgj2t.h dg_ents_*): Node.List with String per
+ * element, Node.StrMap and Node.IntMap as ragged columns. A kind is
+ * DG_ENT_LISTSTR, or DG_ENT_STRMAP / DG_ENT_INTMAP with the value kind in its
+ * low four bits: DG_ENT_BOOL, DG_ENT_INT, DG_ENT_F64 or DG_ENT_STR (the numbers
+ * of DG_COL_BOOL / INT / F64 / STR). A cell is a dg_col_cell; in the cells of a
+ * map kind aux holds the header's type bytes: the key type in bits 0-7, the
+ * value type in bits 8-15. */
+#define DG_ENT_BOOL 1u
+#define DG_ENT_INT 3u
+#define DG_ENT_F64 4u
+#define DG_ENT_STR 5u
+#define DG_ENT_LISTSTR 0x15u /* for e in node.List(): e.String() */
+#define DG_ENT_STRMAP 0x20u  /* Node.StrMap, | the value kind */
+#define DG_ENT_INTMAP 0x40u  /* Node.IntMap, | the value kind */
+
 /* vals (typed column writes, include/dgj2t.h dg_vals_*): a column's kind names
  * the wire encoding to write: a scalar kind is the Thrift wire type itself (2
  * BOOL, 3 I08, 4 DOUBLE, 6 I16, 8 I32, 10 I64, 11 STRING); DG_VAL_LIST | elem
