@@ -33,7 +33,9 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_ents_create", "dg_ents_destroy", "dg_ents_count", "dg_ents_batch_device", "dg_ents_emit_device",
            "dg_ents_batch_host",
            "dg_vals_create", "dg_vals_destroy", "dg_vals_count", "dg_vals_wire_type", "dg_vals_batch_device",
-           "dg_vals_batch_host"]
+           "dg_vals_batch_host",
+           "dg_evals_create", "dg_evals_destroy", "dg_evals_count", "dg_evals_wire_type", "dg_evals_work_bytes",
+           "dg_evals_batch_device", "dg_evals_batch_host"]
 
 _lib = None
 
@@ -155,6 +157,13 @@ def lib() -> C.CDLL:
         "dg_vals_wire_type": (C.c_uint8, [vp, u32]),
         "dg_vals_batch_device": (i32, [vp, vp, vp, u64, u64, vp, u64, vp, vp, vp]),
         "dg_vals_batch_host": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, P64]),
+        "dg_evals_create": (i32, [vp, vp, u32, vp, C.POINTER(vp)]),
+        "dg_evals_destroy": (None, [vp]),
+        "dg_evals_count": (u32, [vp]),
+        "dg_evals_wire_type": (C.c_uint8, [vp, u32]),
+        "dg_evals_work_bytes": (u64, [vp, u64, vp]),
+        "dg_evals_batch_device": (i32, [vp, vp, vp, u64, u64, vp, u64, vp, vp, vp, u64, vp]),
+        "dg_evals_batch_host": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, P64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -201,6 +210,13 @@ class ValCol(C.Structure):
     """dg_val_col (include/dgj2t_defs.h)"""
     _fields_ = [("val", C.c_void_p), ("len", C.c_void_p), ("src", C.c_void_p), ("elem_off", C.c_void_p),
                 ("elems", C.c_void_p), ("present", C.c_void_p)]
+
+
+class EvalCol(C.Structure):
+    """dg_eval_col (include/dgj2t_defs.h)"""
+    _fields_ = [("ent_off", C.c_void_p), ("key", C.c_void_p), ("key_len", C.c_void_p), ("val", C.c_void_p),
+                ("val_len", C.c_void_p), ("key_src", C.c_void_p), ("val_src", C.c_void_p), ("present", C.c_void_p),
+                ("n_ent", C.c_uint64)]
 
 
 class CBTables(C.Structure):

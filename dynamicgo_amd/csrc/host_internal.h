@@ -5,7 +5,7 @@
  * per-stream scratch records, the entry guard, the argument records of one
  * batch, the host batch of the thrift/generic and t2j entries (HostBatch) and the
  * error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host, editm_host, kids_host, cols_host, ents_host, vals_host and j2t_pipe
+ * tget_host, cut_host, editm_host, kids_host, cols_host, ents_host, vals_host, evals_host and j2t_pipe
  * use them).
  */
 #pragma once
@@ -454,6 +454,15 @@ struct dg_vals {
     int16_t field_ids[DG_VALS_MAX_COLS];
 };
 
+/* an entry-value plan (evals_host.hip): K container kinds and, in struct mode, K field ids */
+struct dg_evals {
+    dg_ctx *ctx;
+    uint32_t K;
+    bool ids;
+    uint16_t kinds[DG_VALS_MAX_COLS];
+    int16_t field_ids[DG_VALS_MAX_COLS];
+};
+
 /* one batch of messages (device pointers) and where the lookup's records go */
 struct TGetBatch {
     const uint8_t *src;
@@ -541,6 +550,16 @@ __attribute__((visibility("hidden"))) int dg_i_convert_pack(dg_ctx *c, const dg_
  * nothing */
 __attribute__((visibility("hidden"))) int dg_i_pack_scan(dg_ctx *c, hipStream_t s, const BatchArgs &b, uint8_t *d_dst,
                                                          uint64_t *d_dst_off);
+
+/* a host array's copy on the device (exact size, at least one element; `spare` zeroed elements behind it) */
+template <class T>
+inline int to_device(DevArr<T> &d, const T *h, uint64_t count, uint64_t spare = 0)
+{
+    if (int rc = d.alloc(count + spare + 1)) return rc;
+    if (count) HIPCHK(hipMemcpy(d.p, h, count * sizeof(T), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d.p + count, 0, (spare + 1) * sizeof(T)));
+    return DG_OK;
+}
 
 /* the answer of a host entry to n = 0 */
 inline int empty_batch(uint64_t *off, uint64_t *need)

@@ -125,6 +125,21 @@ TGI void vl_push(VLBytes &h, uint64_t v, uint32_t nb) /* the low nb <= 8 bytes o
     h.n += nb;
 }
 
+/* h at out + at in at most two stores, nothing of it at cap or beyond; h is
+ * empty afterwards and the answer is the position behind it */
+TGI uint64_t vl_flush(VLBytes &h, uint8_t *out, uint64_t at, uint64_t cap)
+{
+    if (at < cap && h.n) {
+        const uint64_t room = cap - at;
+        const uint32_t nb = h.n < room ? h.n : (uint32_t)room;
+        vl_put(out + at, h.lo, nb < 8 ? nb : 8);
+        if (nb > 8) vl_put(out + at + 8, h.hi, nb - 8);
+    }
+    at += h.n;
+    h.lo = h.hi = 0, h.n = 0;
+    return at;
+}
+
 /* what precedes the body of the item z at out + pos, a scalar's bytes (v) and
  * the STOP byte, nothing of it at cap or beyond */
 TGI void vl_head(uint32_t kind, int32_t id, uint32_t fh, uint32_t stop, const VLSize &z, uint64_t v, uint8_t *out,
@@ -139,12 +154,7 @@ TGI void vl_head(uint32_t kind, int32_t id, uint32_t fh, uint32_t stop, const VL
     }
     const bool far_stop = stop && z.len != h.n + 1; /* a body lies between */
     if (stop && !far_stop) vl_push(h, 0, 1);
-    if (pos < cap) {
-        const uint64_t room = cap - pos;
-        const uint32_t nb = h.n < room ? h.n : (uint32_t)room;
-        vl_put(out + pos, h.lo, nb < 8 ? nb : 8);
-        if (nb > 8) vl_put(out + pos + 8, h.hi, nb - 8);
-    }
+    (void)vl_flush(h, out, pos, cap);
     if (far_stop && pos + z.len - 1 < cap) out[pos + z.len - 1] = 0;
 }
 

@@ -88,16 +88,6 @@ static int vals_launch(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, uin
     return DG_OK;
 }
 
-/* a host array's copy on the device (exact size, at least one element) */
-template <class T>
-static int to_device(DevArr<T> &d, const T *h, uint64_t count, uint64_t spare = 0)
-{
-    if (int rc = d.alloc(count + spare + 1)) return rc;
-    if (count) HIPCHK(hipMemcpy(d.p, h, count * sizeof(T), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d.p + count, 0, (spare + 1) * sizeof(T)));
-    return DG_OK;
-}
-
 extern "C" {
 
 int dg_vals_create(dg_ctx *c, const uint8_t *kinds, uint32_t K, const int16_t *field_ids, dg_vals **out)

@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import operator
 import struct
 from typing import List, Optional, Sequence
 
@@ -1474,3 +1475,207 @@ def build_structs_batch(fields, ctx: Optional[Context] = None) -> List[bytes]:
         cols = [_host_column(k, f[2], n, f[3] if len(f) > 3 else None) for k, f in zip(vp.kinds, fields)]
         arena, off, _ = _values_host(vp, cols, n)
         return _split(arena, off[::vp.count])
+
+
+# ---------------------------------------------------------------------------
+# Entry column writes, the inverse of the entry columns above: ragged tensors
+# encoded to list<string>, set<string> and map values (NewNodeList /
+# NewNodeSet / NewNodeMap) or to struct messages of such fields
+# (thrift/generic/node.go:154-187; dg_evals_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+EVAL_MAP = 0x100  # DG_EVAL_MAP
+EVAL_E_RANGE = 2  # DG_EVAL_E_RANGE
+EVALS_MAX_ENT = 0xFFFFFFFF  # DG_EVALS_MAX_ENT
+_EVAL_KEYS = (VAL_I08, VAL_I16, VAL_I32, VAL_I64, VAL_STR)
+_EVAL_VALS = _VAL_ELEMS + (VAL_STR,)
+
+
+def eval_kind(kind) -> int:
+    """A kind as a number (DG_VAL_LIST | 11, DG_VAL_SET | 11, DG_EVAL_MAP | kt
+    << 4 | vt) or by name: ("list", "str"), ("set", "str") (str / string /
+    binary) and ("map", key, value) with key one of byte / i8, i16, i32, i64,
+    str and value any of val_kind's scalar names or str."""
+    k = kind
+    if isinstance(kind, (tuple, list)):
+        try:
+            parts = [_VAL_KINDS[p] if isinstance(p, str) else int(p) for p in kind[1:]]
+        except (KeyError, TypeError, ValueError):
+            raise ValueError("unknown entry value kind %r" % (kind,))
+        if kind[0] in ("list", "set") and parts == [VAL_STR]:
+            k = (VAL_LIST if kind[0] == "list" else VAL_SET) | VAL_STR
+        elif kind[0] == "map" and len(parts) == 2:
+            k = EVAL_MAP | parts[0] << 4 | parts[1]
+        else:
+            raise ValueError("unknown entry value kind %r" % (kind,))
+    try:
+        k = operator.index(k)  # numpy integers too
+    except TypeError:
+        raise ValueError("unknown entry value kind %r" % (kind,))
+    ok = k in (VAL_LIST | VAL_STR, VAL_SET | VAL_STR) or (
+        k & ~0xFF == EVAL_MAP and k >> 4 & 15 in _EVAL_KEYS and k & 15 in _EVAL_VALS)
+    if not ok:
+        raise ValueError("unknown entry value kind %r" % (kind,))
+    return int(k)
+
+
+def _eval_types(kind: int):
+    """(key type or 0, value type) of a kind"""
+    return (kind >> 4 & 15, kind & 15) if kind & EVAL_MAP else (0, VAL_STR)
+
+
+class EntryValuePlan(_Handle):
+    """1 to 16 container columns to write, each a kind (eval_kind), on one
+    context's device (dg_evals). With `field_ids` the plan builds struct
+    messages, as ValuePlan does. .wire_types: the columns' wire types
+    (edit_many_device's val_types)."""
+    _destroy = "dg_evals_destroy"
+
+    def __init__(self, kinds, field_ids=None, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.kinds = [eval_kind(k) for k in kinds]
+        self.field_ids = None if field_ids is None else [int(f) for f in field_ids]
+        if self.field_ids is not None and len(self.field_ids) != len(self.kinds):
+            raise ValueError("%d field ids for %d columns" % (len(self.field_ids), len(self.kinds)))
+        ids = None if self.field_ids is None else np.array(self.field_ids, dtype=np.int16)
+        kk = np.array(self.kinds, dtype=np.uint16)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dg_evals_create(self.ctx.h, kk.ctypes.data, len(self.kinds),
+                                              None if ids is None else ids.ctypes.data, C.byref(h)))
+        self.h = h
+        self.count = int(_lib.lib().dg_evals_count(h))
+        self.wire_types = [int(_lib.lib().dg_evals_wire_type(h, k)) for k in range(self.count)]
+
+    def work_bytes(self, n: int, n_ent) -> int:
+        """the bytes of `work` entry_values_device needs for n messages whose column k holds n_ent[k] entries"""
+        ne = np.array(list(n_ent), dtype=np.uint64)
+        if len(ne) != self.count:
+            raise ValueError("%d entry counts for a plan of %d" % (len(ne), self.count))
+        return max(int(_lib.lib().dg_evals_work_bytes(self.h, n, ne.ctypes.data)), 8)
+
+
+_EVAL_FIELDS = ("ent_off", "key", "key_len", "val", "val_len", "key_src", "val_src", "present")
+
+
+def _eval_cols(cols, count: int):
+    """dg_eval_col[K] from per-column dicts of tensors, arrays or raw pointers and the int n_ent"""
+    if len(cols) != count:
+        raise ValueError("%d columns for a plan of %d" % (len(cols), count))
+    recs = (_lib.EvalCol * count)()
+    for r, c in zip(recs, cols):
+        for f in _EVAL_FIELDS:
+            x = c.get(f)
+            setattr(r, f, x.ctypes.data if isinstance(x, np.ndarray) else _ptr(x))
+        r.n_ent = int(c["n_ent"])
+    return recs
+
+
+def entry_values_device(plan: EntryValuePlan, cols, n: int, out, out_off, work, status=None, out_base: int = 0,
+                        cap: Optional[int] = None, stream=None):
+    """Device-resident batch (dg_evals_batch_device) over torch tensors or raw
+    device pointers. cols: one dict per column in the shapes entry_emit_device
+    writes: ent_off int64[n + 1], key / val int64 per entry, key_len / val_len
+    int32 per entry, key_src / val_src uint8 (16 spare bytes; the thrift arena
+    for both when the tensors come from entry_emit_device), present uint8[n]
+    (struct mode, optional), and n_ent, the entries the arrays hold (an int: no
+    read-back). A list kind's elements are val / val_len / val_src. out
+    uint8[cap + 16] or None (sizing); out_off int64[n * K + 1]; status uint8[n
+    * K] or None; work a uint8 tensor of plan.work_bytes(n, [n_ent...]) bytes,
+    this call's alone until it has run. Asynchronous on `stream`."""
+    s = _stream_handle(stream, out_off)
+    if cap is None:
+        cap = int(out.numel()) - 16 if hasattr(out, "numel") else 0
+    wb = int(work.numel()) * int(work.element_size()) if hasattr(work, "numel") else plan.work_bytes(n, [c["n_ent"] for c in cols])
+    _lib.check(_lib.lib().dg_evals_batch_device(plan.ctx.h, plan.h, _eval_cols(cols, plan.count), n, out_base, _ptr(out),
+                                                max(cap, 0), _ptr(out_off), _ptr(status), _ptr(work), wb, s))
+
+
+def _host_entry_column(kind: int, column, n: int, present=None):
+    """a column of entry_values_batch as the arrays dg_evals_batch_host reads"""
+    if len(column) != n:
+        raise ValueError("a column of %d values for %d messages" % (len(column), n))
+    kt, vt = _eval_types(kind)
+    rows = [list(r.items()) if isinstance(r, dict) else list(r) for r in column]
+    if not kt:
+        rows = [[(None, e) for e in r] for r in rows]
+    flat = [e for r in rows for e in r]
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(r) for r in rows], out=off[1:])
+    c = {"ent_off": off, "n_ent": len(flat)}
+    for t, side, x in ((kt, "key", 0), (vt, "val", 1)):
+        if not t:
+            continue
+        if t == VAL_STR:
+            pay = [e[x].encode() if isinstance(e[x], str) else bytes(e[x]) for e in flat]
+            lens = np.fromiter((len(p) for p in pay), dtype=np.uint64, count=len(pay))
+            c[side] = (np.cumsum(lens) - lens).astype(np.uint64)
+            c[side + "_len"] = lens.astype(np.uint32)
+            c[side + "_src"] = np.frombuffer(b"".join(pay) + b"\0" * 16, dtype=np.uint8)
+        else:
+            vals = [e[x] for e in flat]
+            c[side] = _as_u64(np.asarray(vals, dtype=np.float64 if t == VAL_F64 else None), t) if vals else \
+                np.zeros(0, dtype=np.uint64)
+    if present is not None:
+        c["present"] = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+        if len(c["present"]) != n:
+            raise ValueError("present of %d entries for %d messages" % (len(c["present"]), n))
+    return c
+
+
+def _entry_values_host(plan: EntryValuePlan, cols, n: int):
+    lib = _lib.lib()
+    k = plan.count
+    off = np.zeros(n * k + 1, dtype=np.uint64)
+    status = np.zeros(n * k, dtype=np.uint8)
+    need = C.c_uint64(0)
+    recs = _eval_cols(cols, k)
+    for sized in (False, True):  # the first call sizes: the arena's bytes are known exactly after it
+        cap = int(need.value) if sized else 0
+        out = np.zeros(cap, dtype=np.uint8)
+        _lib.check(lib.dg_evals_batch_host(plan.ctx.h, plan.h, recs, n, out.ctypes.data if cap else None, cap,
+                                           off.ctypes.data, status.ctypes.data, C.byref(need)))
+        if not need.value:
+            break
+    return out, off, status
+
+
+def entry_values_batch(columns, plan, ctx: Optional[Context] = None):
+    """The host path (dg_evals_batch_host): `plan` is an EntryValuePlan or a
+    list of kinds; a list column is a sequence of sequences of str / bytes, a
+    map column a sequence of dicts or of sequences of (key, value) pairs (pairs
+    keep their order and their duplicates). Returns (arena uint8, off uint64[n
+    * K + 1], status uint8[n * K]), message-major as values_batch's."""
+    ep = plan if isinstance(plan, EntryValuePlan) else EntryValuePlan(plan, None, ctx)
+    with _unless_given(ep, plan):
+        if len(columns) != ep.count:
+            raise ValueError("%d columns for a plan of %d" % (len(columns), ep.count))
+        n = len(columns[0])
+        return _entry_values_host(ep, [_host_entry_column(k, c, n) for k, c in zip(ep.kinds, columns)], n)
+
+
+def set_entry_columns_batch(msgs: Sequence[bytes], parent, columns, desc=None, root_type: int = STRUCT,
+                            ctx: Optional[Context] = None) -> List[EditManyResult]:
+    """SetMany from entry columns, the counterpart of set_columns_batch: below
+    the node at `parent`, every (step, kind, column) sets the child at `step`
+    of message i to column[i] encoded as the container `kind`."""
+    columns = list(columns)
+    if not 1 <= len(columns) <= EDITM_MAX_ITEMS:
+        raise ValueError("%d columns (1 to %d)" % (len(columns), EDITM_MAX_ITEMS))
+    with EntryValuePlan([c[1] for c in columns], None, ctx) as ep:
+        if any(len(c[2]) != len(msgs) for c in columns):
+            raise ValueError("a column's length is not the batch's")
+        arena, off, _ = entry_values_batch([c[2] for c in columns], ep) if msgs else (np.zeros(0, np.uint8), np.zeros(1, np.uint64), None)
+        with EditManyPlan(parent, [c[0] for c in columns], EDIT_SET, desc, ctx) as plan:
+            return _editm_batch(msgs, plan, None, ep.wire_types, root_type, encoded=(arena, off))
+
+
+def build_entry_structs_batch(fields, ctx: Optional[Context] = None) -> List[bytes]:
+    """The counterpart of build_structs_batch for container fields: `fields`
+    is a list of (field_id, kind, column[, present]); message i holds, in the
+    order given, every field whose present[i] is true (all, without present),
+    then STOP."""
+    fields = [tuple(f) for f in fields]
+    n = len(fields[0][2])
+    with EntryValuePlan([f[1] for f in fields], [f[0] for f in fields], ctx) as ep:
+        cols = [_host_entry_column(k, f[2], n, f[3] if len(f) > 3 else None) for k, f in zip(ep.kinds, fields)]
+        arena, off, _ = _entry_values_host(ep, cols, n)
+        return _split(arena, off[::ep.count])

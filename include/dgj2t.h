@@ -1081,7 +1081,8 @@ int dg_ents_batch_host(dg_ctx *ctx, const dg_ents *ents, uint8_t root_type, cons
  *                      Count 0 is legal: the kind names the element type
  *                      (WriteAny refuses an empty []interface{}).
  * Lists of strings, structs or containers, maps, and descriptor-aware writes
- * (WriteAnyWithDesc) are not part of this.
+ * (WriteAnyWithDesc) are not part of this: lists and sets of strings and maps
+ * are dg_evals_* below, the rest stays out.
  *
  * Cell errors: a STRING length or a list count above 2^31 - 1, or an item
  * (the value and, in struct mode, its field header and STOP) of 2^32 bytes or
@@ -1129,6 +1130,94 @@ int dg_vals_batch_device(dg_ctx *ctx, const dg_vals *plan, const dg_val_col *col
  * otherwise DG_E_NOMEM when cap < *need. */
 int dg_vals_batch_host(dg_ctx *ctx, const dg_vals *plan, const dg_val_col *cols, uint64_t n, uint8_t *out, uint64_t cap,
                        uint64_t *out_off, uint8_t *status, uint64_t *need);
+
+/* ------------------------------------------------------------------------
+ * evals: entry column writes, the inverse of ents and a component beside vals
+ * (dg_vals_* takes none of these kinds): ragged tensors encoded to list<string>,
+ * set<string> and map values (the reference's NewNodeList / NewNodeSet /
+ * NewNodeMap, thrift/generic/node.go:154-187, over WriteAny,
+ * thrift/binary.go:1480-1660) or, with field ids, to struct messages of such
+ * fields. A plan holds K columns, 1 <= K <= DG_VALS_MAX_COLS, each with a
+ * uint16_t kind (dgj2t_defs.h): DG_VAL_LIST | 11, DG_VAL_SET | 11, or
+ * DG_EVAL_MAP | kt << 4 | vt with kt one of 3, 6, 8, 10, 11 and vt one of 2, 3,
+ * 4, 6, 8, 10, 11. dg_evals_create answers DG_E_ARG ("column j: unknown kind
+ * N") for any other kind, and for another K.
+ *
+ * What cell (i, k) writes, from column k's dg_eval_col: message i owns the
+ * entries [d_ent_off[i], d_ent_off[i + 1]) of the per-entry arrays, in the
+ * shapes dg_ents_emit_device writes them (its outputs plug in unchanged, with
+ * d_thrift as both arenas).
+ *   list / set   0B, the i32 big-endian count, then every element: its i32
+ *                length d_val_len[e] and the bytes at d_val_src + d_val[e].
+ *   map          kt, vt, the i32 count, then every entry as its key followed
+ *                by its value. A scalar is encoded as dg_vals encodes it (BOOL:
+ *                1 for any non-zero input; integers: the low bits big-endian;
+ *                DOUBLE: the eight bytes swapped), a string as its i32 length
+ *                and payload.
+ * Struct mode (field_ids given) is dg_vals': the 3-byte field header before
+ * every item, STOP behind a message's last, d_present[i] == 0 leaves the field
+ * out, and a d_present pointer without field ids is DG_E_ARG at the call.
+ *
+ * Deviations from the reference:
+ *   1. Count 0 is legal: the kind names the types (WriteAny refuses an empty
+ *      container).
+ *   2. Entries are written in input order and a key given twice is written
+ *      twice (a Go map has no order and no duplicates).
+ *   3. Struct and container values, map[interface{}], WriteAnyWithDesc and keys
+ *      of other types stay out.
+ *   4. A plan holds entry kinds only: a message of scalar and entry columns
+ *      takes two calls, dg_vals in struct mode and then dg_editm (set_many) to
+ *      insert the containers.
+ *
+ * Cell errors; a flagged cell is written as the empty container of its kind
+ * (0B 00 00 00 00; kt vt 00 00 00 00), so the arena always holds well-formed
+ * Thrift, and none of its entries' payload bytes is read:
+ *   DG_VAL_E_SIZE     a count above 2^31 - 1, any key or value length of the
+ *                     cell above 2^31 - 1, or an item of 2^32 bytes or more.
+ *   DG_EVAL_E_RANGE   d_ent_off[i] > d_ent_off[i + 1], or d_ent_off[i + 1] >
+ *                     n_ent. RANGE is tested first.
+ * No entry at an index >= n_ent is ever read. Entry ranges may overlap or leave
+ * gaps: every cell reads its own range.
+ */
+typedef struct dg_evals dg_evals;
+int dg_evals_create(dg_ctx *ctx, const uint16_t *kinds, uint32_t K, const int16_t *field_ids, dg_evals **out);
+void dg_evals_destroy(dg_evals *p);
+uint32_t dg_evals_count(const dg_evals *p);
+/* the wire type of column k's values (dg_editm_batch_device's val_types[k]):
+ * 15 for a list, 14 for a set, 13 for a map; 0 for no such column */
+uint8_t dg_evals_wire_type(const dg_evals *p, uint32_t k);
+/* the bytes of d_work a batch of n messages needs whose column k holds
+ * n_ent[k] entries (K values): the cells' lengths, counts and scanned counts,
+ * per variable-stride column 12 bytes an entry (its encoded size and its
+ * position), and the scans' tile sums. 0 for a NULL argument, n >= 2^32 or an
+ * n_ent above DG_EVALS_MAX_ENT. */
+uint64_t dg_evals_work_bytes(const dg_evals *p, uint64_t n, const uint64_t *n_ent);
+
+/* Device buffers, stream-ordered, async (stream NULL: the context's). cols: K
+ * records in HOST memory whose pointers are device pointers. The outputs are
+ * dg_vals_batch_device's message-major arena: d_out_off (u64, n * K + 1
+ * entries, 8-byte aligned), [0] = out_base, the last entry the arena's end;
+ * d_out with cap + 16 bytes allocated, nothing stored at an index >= cap and
+ * the 16 spare bytes untouched; d_status (u8, n * K) may be NULL. d_out NULL
+ * stops after the offsets and statuses (sizing). n = 0 returns DG_OK and
+ * launches nothing. d_work (8-byte aligned, work_bytes >=
+ * dg_evals_work_bytes, else DG_E_NOMEM) is the call's only storage: nothing is
+ * allocated, and calls on several streams need a d_work each. An n_ent above
+ * DG_EVALS_MAX_ENT is DG_E_ARG. Per variable-stride column (a string key, a
+ * string value, list elements) an entry-size pass, one lane per entry, and
+ * cols' scan; then for all columns at once a cell pass, the scans of the
+ * cells' lengths (into d_out_off) and counts, a head pass and ONE
+ * entry-parallel emit over the entries of every column, in which a lane writes
+ * one entry's key and value whatever the containers' sizes are. */
+int dg_evals_batch_device(dg_ctx *ctx, const dg_evals *plan, const dg_eval_col *cols, uint64_t n, uint64_t out_base,
+                          uint8_t *d_out, uint64_t cap, uint64_t *d_out_off, uint8_t *d_status, void *d_work,
+                          uint64_t work_bytes, void *stream);
+/* Host buffers, synchronous (no spare bytes needed, no d_work): cols' pointers
+ * are host pointers, out_off (n * K + 1, never NULL) starts at 0, status may be
+ * NULL. *need = the arena's bytes. out NULL with cap 0 stops there (sizing);
+ * otherwise DG_E_NOMEM when cap < *need. */
+int dg_evals_batch_host(dg_ctx *ctx, const dg_evals *plan, const dg_eval_col *cols, uint64_t n, uint8_t *out, uint64_t cap,
+                        uint64_t *out_off, uint8_t *status, uint64_t *need);
 
 /* Timing helper for benchmarks: launch the device batch `iters` times on the
  * context stream bracketed by HIP events; returns total milliseconds of GPU

@@ -350,6 +350,33 @@ typedef struct dg_val_col {
     const uint8_t *d_present;   /* n or NULL (all present); struct mode only: 0 leaves the field out of the message */
 } dg_val_col;
 
+/* evals (entry column writes, include/dgj2t.h dg_evals_*), the inverse of
+ * ents: a kind is a uint16_t. DG_VAL_LIST | 11 and DG_VAL_SET | 11 are a list
+ * and a set of strings or binaries; DG_EVAL_MAP | kt << 4 | vt is a map with
+ * the key's wire type kt (3, 6, 8, 10 or 11) and the value's vt (2, 3, 4, 6, 8,
+ * 10 or 11). A cell's status is DG_VAL_OK, DG_VAL_E_SIZE or DG_EVAL_E_RANGE. */
+#define DG_EVAL_MAP 0x100u
+#define DG_EVAL_E_RANGE 2u /* d_ent_off[i] > d_ent_off[i + 1], or d_ent_off[i + 1] > n_ent: the cell is written as the
+                              empty container of its kind */
+#define DG_EVALS_MAX_ENT 0xFFFFFFFFull /* the most entries one column's arrays may hold (n_ent) */
+/* one column's inputs, in the shapes dg_ents_emit_device writes (device
+ * pointers at the device entry, host pointers at the host entry); what a kind
+ * does not read may be NULL, and so may everything but d_ent_off when n_ent is
+ * 0. The list kinds' elements are d_val / d_val_len / d_val_src. */
+typedef struct dg_eval_col {
+    const uint64_t *d_ent_off; /* n + 1: message i owns the entries [d_ent_off[i], d_ent_off[i + 1]) */
+    const uint64_t *d_key;     /* per entry: an int key (its low bits are written at the key's width); a string key:
+                                  the payload's byte offset in d_key_src */
+    const uint32_t *d_key_len; /* per entry, string keys: the payload's length */
+    const uint64_t *d_val;     /* per entry: a scalar (DOUBLE: its bits); a string: the payload's offset in d_val_src */
+    const uint32_t *d_val_len; /* per entry, string values and list elements: the payload's length */
+    const uint8_t *d_key_src;  /* the arenas the offsets point into, 16 readable bytes after the last payload byte */
+    const uint8_t *d_val_src;
+    const uint8_t *d_present;  /* n or NULL (all present); struct mode only: 0 leaves the field out of the message */
+    uint64_t n_ent;            /* the entries the four per-entry arrays hold, at most DG_EVALS_MAX_ENT: no entry at
+                                  an index >= n_ent is read, and the launch geometry comes from it */
+} dg_eval_col;
+
 /* t2j (Thrift binary -> JSON, conv/t2j) option bits: the conv.Options fields
  * conv/t2j/impl.go reads (conv/api.go:52-121) */
 #define DG_T2J_BYTE_AS_UINT8 (1ull << 0)     /* ByteAsUint8 */
