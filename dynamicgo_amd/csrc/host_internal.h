@@ -5,7 +5,7 @@
  * per-stream scratch records, the entry guard, the argument records of one
  * batch, the host batch of the thrift/generic and t2j entries (HostBatch) and the
  * error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host, editm_host, kids_host, cols_host, ents_host, vals_host, evals_host and j2t_pipe
+ * tget_host, cut_host, editm_host, kids_host, cols_host, ents_host, rows_host, vals_host, evals_host and j2t_pipe
  * use them).
  */
 #pragma once
@@ -355,6 +355,15 @@ struct dg_ctx {
     DevArr<uint32_t> ents_list, ents_cnt_buf;
     AltCounters ents_cnt;
     DevArr<uint64_t> ents_sums;
+    /* rows (rows_host.hip): the deep frames of its three lane passes (32 MB,
+     * allocated by the first call), their queue, two alternating queue
+     * counters, the heads' counts (n) and the scan's tile sums, and the row
+     * index of a call that gives none: its own, like cols' */
+    SharedWs rows;
+    DevArr<uint32_t> rows_list, rows_cnt_buf, rows_counts;
+    AltCounters rows_cnt;
+    DevArr<uint64_t> rows_sums;
+    DevArr<dg_row_ent> rows_index;
     /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB) */
     SharedWs t2j_tok;
     /* t2j deep pass: T2J_DEEP_DEPTH frames per lane (about 100 MB, allocated
@@ -443,6 +452,15 @@ struct dg_ents {
     DevArr<uint8_t> d_blob;
     dg_path_hdr hdr;
     uint8_t kinds[DG_TGET_MAX_PATHS];
+};
+
+/* a row-column plan (rows_host.hip): the parent's path set of one path, the
+ * sub-paths' set and one DG_COL_* kind per sub-path */
+struct dg_rows {
+    dg_ctx *ctx;
+    DevArr<uint8_t> d_blob, d_sub;
+    dg_path_hdr hdr, sub_hdr;
+    uint8_t kinds[DG_ROWS_MAX_COLS];
 };
 
 /* a value plan (vals_host.hip): K kinds and, in struct mode, K field ids */

@@ -1,7 +1,9 @@
 """thrift/generic on the GPU. Typed column writes (the last part of this
 module: ValuePlan, values_batch, values_device, set_columns_batch,
-build_structs_batch: the NewNode* constructors over tensors), entry columns
-(the part before it: EntryPlan, entries_batch, entries_device,
+build_structs_batch: the NewNode* constructors over tensors), row columns
+(RowPlan, rows_batch, rows_device, row_list_device: the fields of every element
+of a list as ragged tensors), entry columns
+(the part before them: EntryPlan, entries_batch, entries_device,
 entry_emit_device: GetByPath followed by Node.List of strings / StrMap / IntMap
 as ragged tensors), typed column
 reads (the part before that: ColumnPlan, columns_batch, columns_device, column_list_device:
@@ -104,6 +106,11 @@ def _resolve(path: Sequence[Path], desc) -> List[Path]:
     """PathFieldName -> PathFieldId through the descriptor, walking it along
     the path as Value.GetByPath does (value.go:118-143): a field step moves to
     the field's type, an index or key step to the element type."""
+    return _resolve_to(path, desc)[0]
+
+
+def _resolve_to(path: Sequence[Path], desc):
+    """_resolve's steps and the descriptor the path ends at (None when it is not known)."""
     out = []
     d = desc
     for st in path:
@@ -124,7 +131,7 @@ def _resolve(path: Sequence[Path], desc) -> List[Path]:
             d = f.type if f is not None else None
         else:
             d = d.elem
-    return out
+    return out, d
 
 
 def compile_paths(paths: Sequence[Sequence[Path]], desc=None) -> bytes:
@@ -1122,6 +1129,177 @@ def columns_batch(msgs: Sequence[bytes], columns, desc=None, root_type: int = ST
             else:
                 c.values = val[k].view(np.int64)
             out.append(c)
+        return out
+
+
+# ---------------------------------------------------------------------------
+# Row columns: the fields of every element of a list or set as ragged columns:
+# GetByPath(parent), Children one level, then GetByPath(sub) and a cast per
+# element (dg_rows_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+ROWS_MAX_COLS = 8  # DG_ROWS_MAX_COLS
+ROWS_HEAD_DTYPE = np.dtype([("first", "<u8"), ("count", "<u4"), ("status", "u1"), ("type", "u1"), ("elem_type", "u1"),
+                            ("step", "u1")])  # dg_rows_head
+ROW_ENT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("msg", "<u4")])  # dg_row_ent
+
+
+class RowPlan(_Handle):
+    """One parent path (a list of Path steps, () for the message's root) and 1
+    to 8 row columns, each (sub_path, kind): the sub-path is looked up in every
+    element of the list or set the parent path ends at, the kind is col_kind's.
+    PathFieldName steps of the parent are resolved through `desc`, those of a
+    sub-path through the descriptor of the list's elements; a name step
+    without a descriptor raises (dg_rows)."""
+    _destroy = "dg_rows_destroy"
+
+    def __init__(self, parent, columns, desc=None, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.kinds = [col_kind(k) for _, k in columns]
+        steps, at = _resolve_to(list(parent), desc)
+        self.parent_blob = compile_paths([steps])
+        self.blob = compile_paths([list(p) for p, _ in columns], at.elem if at is not None else None)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dg_rows_create(self.ctx.h, self.parent_blob, len(self.parent_blob), self.blob, len(self.blob),
+                                             bytes(self.kinds), len(self.kinds), C.byref(h)))
+        self.h = h
+        self.count = int(_lib.lib().dg_rows_count(h))
+        self.lists = [k for k, kind in enumerate(self.kinds) if kind & COL_LIST]
+
+
+def rows_device(plan: RowPlan, thrift, in_off, n: int, head, row_off, index=None, val=None, cell=None, lens=None,
+                row_cap: int = 0, root_type: int = STRUCT, stream=None, max_len: int = 0):
+    """Device-resident batch (dg_rows_batch_device) over torch tensors or raw
+    device pointers: thrift uint8[>= in_off[n] + 16]; in_off int64[n + 1]; head
+    n 16-byte heads (e.g. int32 of shape (n, 4)); row_off int64[n + 1]
+    ([n] = the total R); index row_cap 16-byte entries or None (the plan's
+    context keeps it); val int64[P, row_cap], cell P * row_cap 8-byte cells
+    (e.g. int32 of shape (P, row_cap, 2)), lens int32[P, row_cap] (None when no
+    column is str or a list). val and cell None: the sizing call (heads and
+    row_off; with index given, the index too). No row at an
+    index >= row_cap is stored. Asynchronous on `stream` (a torch stream, a raw
+    stream handle, or None for torch's current stream when `thrift` is a
+    tensor)."""
+    s = _stream_handle(stream, thrift)
+    _lib.check(_lib.lib().dg_rows_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n, _ptr(head),
+                                               _ptr(row_off), _ptr(index), _ptr(val), _ptr(cell), _ptr(lens), row_cap, s,
+                                               max_len))
+
+
+def row_list_device(plan: RowPlan, k: int, thrift, n_rows: int, val_k, cell_k, len_k, elem_off, elems, elem_cap: int,
+                    stream=None):
+    """List-kind row column k's elements (dg_rows_list_device) behind
+    rows_device on the same stream: val_k / cell_k / len_k are column k's rows
+    of its outputs, n_rows the rows whose cells were written; elem_off
+    int64[n_rows + 1] receives the scanned counts, elems int64[elem_cap] the
+    elements, or None to stop after the scan."""
+    s = _stream_handle(stream, thrift)
+    _lib.check(_lib.lib().dg_rows_list_device(plan.ctx.h, plan.h, k, _ptr(thrift), n_rows, _ptr(val_k), _ptr(cell_k),
+                                              _ptr(len_k), _ptr(elem_off), _ptr(elems), elem_cap, s))
+
+
+def rows_records(msgs: Sequence[bytes], plan: RowPlan, root_type: int = STRUCT, count_only: bool = False):
+    """The raw outputs of dg_rows_batch_host: (head ROWS_HEAD_DTYPE[n], row_off
+    uint64[n + 1], index ROW_ENT_DTYPE[R], val uint64[P, R], cell
+    COL_CELL_DTYPE[P, R], lens uint32[P, R], arena); offsets point into `arena`,
+    the messages back to back. count_only stops after the heads (R = 0 rows
+    come back): head["count"] is batched Node.Len."""
+    n, P = len(msgs), plan.count
+    lib = _lib.lib()
+    head = np.zeros(n, dtype=ROWS_HEAD_DTYPE)
+    row_off = np.zeros(n + 1, dtype=np.uint64)
+    need = C.c_uint64(0)
+
+    def outs(R):
+        return (np.zeros(R, dtype=ROW_ENT_DTYPE), np.zeros((P, R), dtype=np.uint64), np.zeros((P, R), dtype=COL_CELL_DTYPE),
+                np.zeros((P, R), dtype=np.uint32))
+
+    if n == 0:
+        _lib.check(lib.dg_rows_batch_host(plan.ctx.h, plan.h, root_type, None, None, 0, None, row_off.ctypes.data, None, None,
+                                          None, None, 0, C.byref(need)))
+        return (head, row_off) + outs(0) + (np.zeros(16, dtype=np.uint8),)
+    arena, in_off = _arena(msgs)
+    _lib.check(lib.dg_rows_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
+                                      head.ctypes.data, row_off.ctypes.data, None, None, None, None, 0, C.byref(need)))
+    R = 0 if count_only else int(need.value)
+    index, val, cell, lens = outs(R)
+    if R:
+        _lib.check(lib.dg_rows_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
+                                          head.ctypes.data, row_off.ctypes.data, index.ctypes.data, val.ctypes.data,
+                                          cell.ctypes.data, lens.ctypes.data, R, C.byref(need)))
+    return head, row_off, index, val, cell, lens, arena
+
+
+def _row_list_elems(plan: RowPlan, k: int, arena, val_k, cell_k, len_k):
+    """(elem_off int64[R + 1], elems uint64) of list-kind row column k: the host
+    arrays of rows_records through dg_rows_list_device."""
+    import torch
+    R = len(val_k)
+    dev = torch.device("cuda", plan.ctx.device)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream()
+        d_arena = torch.from_numpy(np.array(arena)).to(dev)
+        d_val = torch.from_numpy(val_k.view(np.int64).copy()).to(dev)
+        d_cell = torch.from_numpy(cell_k.copy().view(np.int64)).to(dev)
+        d_len = torch.from_numpy(len_k.view(np.int32).copy()).to(dev)
+        total = int(len_k.astype(np.uint64).sum())
+        d_off = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        d_el = torch.zeros(max(total, 1), dtype=torch.int64, device=dev)
+        row_list_device(plan, k, d_arena, R, d_val, d_cell, d_len, d_off, d_el if total else None, total, stream=s)
+        s.synchronize()
+        return d_off.cpu().numpy(), d_el.cpu().numpy()[:total].view(np.uint64)
+
+
+class Rows:
+    """What rows_batch returns: .head (ROWS_HEAD_DTYPE[n]: status, step, type,
+    elem_type, count, first), .status (uint8[n]), .error(i) (None,
+    "ErrNotFound", "ErrRead", "ErrDismatchType" or "ErrUnsupportedType"),
+    .offsets (int64[n + 1]: message i owns rows offsets[i]:offsets[i + 1]),
+    .index (ROW_ENT_DTYPE[R]: every row's element span in the arena and its
+    message) and .columns, one Column per row column over the R rows (a list
+    kind's .offsets index its elements by row)."""
+    __slots__ = ("head", "status", "offsets", "index", "columns")
+
+    def error(self, i: int):
+        return COL_ERROR_NAMES.get(int(self.status[i]), "ErrRead")
+
+    def __repr__(self):
+        return "Rows(%d messages, %d rows, %d columns)" % (len(self.status), len(self.index), len(self.columns))
+
+
+def rows_batch(msgs: Sequence[bytes], parent, columns=None, desc=None, root_type: int = STRUCT,
+               ctx: Optional[Context] = None) -> Rows:
+    """For every message the list or set at `parent` and, for every element of
+    it, GetByPath(sub_path) and a cast: `columns` is a list of (sub_path, kind);
+    `parent` may be a RowPlan instead (then `columns` is not given)."""
+    plan = parent if isinstance(parent, RowPlan) else RowPlan(parent, columns, desc, ctx)
+    with _unless_given(plan, parent):
+        head, row_off, index, val, cell, lens, arena = rows_records(msgs, plan, root_type)
+        out = Rows()
+        out.head, out.status, out.offsets, out.index = head, head["status"], row_off.astype(np.int64), index
+        out.columns = []
+        for k, kind in enumerate(plan.kinds):
+            c = Column()
+            c.kind, c.status, c.type, c.step, c.aux = kind, cell[k]["status"], cell[k]["type"], cell[k]["step"], cell[k]["aux"]
+            c.valid = c.status == OK
+            c.offsets = c.lengths = None
+            if kind & COL_LIST:
+                eo, elems = _row_list_elems(plan, k, arena, val[k], cell[k], lens[k]) if len(index) else \
+                    (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.uint64))
+                c.values = elems.view(np.float64) if kind == COL_LIST_F64 else elems.view(np.int64)
+                c.offsets, c.lengths = eo, lens[k]
+            elif kind == COL_STR:
+                c.offsets, c.lengths = val[k].astype(np.int64), lens[k]
+                c.values = [arena[int(o):int(o) + int(ln)].tobytes() if ok else b""
+                            for o, ln, ok in zip(c.offsets, c.lengths, c.valid)]
+            elif kind == COL_BOOL:
+                c.values = val[k] != 0
+            elif kind == COL_BYTE:
+                c.values = val[k].astype(np.uint8)
+            elif kind == COL_F64:
+                c.values = val[k].view(np.float64)
+            else:
+                c.values = val[k].view(np.int64)
+            out.columns.append(c)
         return out
 
 

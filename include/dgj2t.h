@@ -953,6 +953,94 @@ int dg_cols_batch_host(dg_ctx *ctx, const dg_cols *cols, uint8_t root_type, cons
                        uint64_t *elem_off, uint64_t *elems, uint64_t elem_cap, uint64_t *need);
 
 /* ------------------------------------------------------------------------
+ * rows: row columns, the fields of every element of a list or set as ragged
+ * columns: what the reference's loop
+ *     v.GetByPath(parent...).Children(&kids, false, opts)
+ *     for each kid: kid.Node.GetByPath(sub_k...) and the cast of column k
+ * gives ("the price and the SKU of every line item of every order"). A plan is
+ * ONE parent path (a path set of exactly one path; the empty path is the
+ * message's root) plus 1 to DG_ROWS_MAX_COLS row columns, each a sub-path (it
+ * may be empty) and a kind of cols (DG_COL_*). A component beside cols, ents
+ * and kids: none of their entries changes.
+ *
+ *   head (message i)   the parent is looked up and its children scanned as
+ *                      dg_kids_* does without DG_KIDS_F_RECURSE: a failed
+ *                      lookup gives its status and step; under a non-empty
+ *                      path the node is skipped first (a failure there is
+ *                      DG_TGET_E_READ, step = the path's length) and its depth
+ *                      budget starts one lower; a node that is not LIST or SET
+ *                      is DG_COL_E_UNSUPPORTED with type = the wire type found
+ *                      (a STRUCT or MAP parent too: dg_kids_* serves those);
+ *                      the header is read as ReadListBegin reads it; an
+ *                      element whose skip fails makes the message
+ *                      DG_TGET_E_READ with no rows. OK: count = Node.Len().
+ *   rows               d_row_off (u64, n + 1) is the exclusive scan of the
+ *                      counts, d_row_off[n] the total R. Row d_row_off[i] + j
+ *                      is element j of message i's list, in wire order; its
+ *                      index entry (dg_row_ent) holds the element's arena
+ *                      offset, its byte length and i.
+ *   cell (g, k)        GetByPath(sub_k...) on the element's own bytes with the
+ *                      list's element type as the root type and a fresh skip
+ *                      budget, then column k's cast: a dg_cols_* cell, with
+ *                      step counting within the sub-path. The lookup ends at
+ *                      the element's end: a field that element j lacks and
+ *                      element j + 1 has is DG_TGET_NOT_FOUND for row j. STR
+ *                      and list cells hold arena offsets, as cols' do.
+ * Children's storage options have no counterpart.
+ */
+typedef struct dg_rows dg_rows;
+/* parent_blob: dg_path_create's blob of exactly one path; sub_blob: one of
+ * n_kinds paths, kinds as dg_cols_create takes them (DG_E_ARG with a text
+ * otherwise). */
+int dg_rows_create(dg_ctx *ctx, const void *parent_blob, size_t parent_len, const void *sub_blob, size_t sub_len,
+                   const uint8_t *kinds, uint32_t n_kinds, dg_rows **out);
+void dg_rows_destroy(dg_rows *p);
+uint32_t dg_rows_count(const dg_rows *p);
+
+/* Device buffers, stream-ordered, async (stream NULL: the context's), all
+ * passes on the one stream with no host round trip: head/count pass -> scan ->
+ * index pass -> row cell pass, each lane pass followed by its deep pass.
+ * Messages, root_type and the 16 readable bytes past the arena's end as
+ * dg_tget_batch_device; n below 2^32. d_head (n entries) and d_index are
+ * 16-byte aligned, d_row_off has n + 1 entries. Outputs are column-major over
+ * row_cap, P = the plan's column count: d_val (u64), d_cell (dg_col_cell) and
+ * d_len (u32, NULL allowed when no column is STR or a list) hold P * row_cap
+ * entries, column k at [k * row_cap, ...), the first two 8-byte aligned.
+ * d_index (row_cap entries) may be NULL: the index then lives in the
+ * component's own scratch. Rows [0, min(R, row_cap)) are indexed and their
+ * cells written; no index entry and no cell of a row >= row_cap is ever stored
+ * and d_row_off[n] still tells the need. d_val and d_cell NULL is the sizing
+ * call: heads and d_row_off only (with d_index given, the index as well: the
+ * first two passes and the third). row_cap * P must stay below 2^32
+ * (DG_E_INVALID with a text). n = 0 writes d_row_off[0] = 0 and launches
+ * nothing else. The deep passes' queue, counters and frames and the scan's
+ * tile sums are the component's own. max_len: a hint. */
+int dg_rows_batch_device(dg_ctx *ctx, const dg_rows *rows, uint8_t root_type, const uint8_t *d_thrift,
+                         const uint64_t *d_in_off, uint64_t n, dg_rows_head *d_head, uint64_t *d_row_off,
+                         dg_row_ent *d_index, uint64_t *d_val, dg_col_cell *d_cell, uint32_t *d_len, uint64_t row_cap,
+                         void *stream, uint64_t max_len);
+/* The elements of list-kind row column k after dg_rows_batch_device on the
+ * same stream (or ordered behind it), as dg_cols_list_device over rows: n_rows
+ * = the rows whose cells were written (min(R, row_cap)), d_val_k / d_cell_k /
+ * d_len_k column k's parts of its outputs (d_val + k * row_cap, ...). A scan
+ * fills d_elem_off (u64, n_rows + 1 entries); row g's elements go to
+ * d_elems[d_elem_off[g], d_elem_off[g + 1]), 8 bytes each. d_elems NULL stops
+ * after the scan; no element is stored at an index >= elem_cap. DG_E_ARG when k
+ * names no list column. */
+int dg_rows_list_device(dg_ctx *ctx, const dg_rows *rows, uint32_t k, const uint8_t *d_thrift, uint64_t n_rows,
+                        const uint64_t *d_val_k, const dg_col_cell *d_cell_k, const uint32_t *d_len_k,
+                        uint64_t *d_elem_off, uint64_t *d_elems, uint64_t elem_cap, void *stream);
+/* Host buffers, synchronous (no spare bytes needed): head (n) and row_off
+ * (n + 1) are always filled and *need = row_off[n] = R. index, val, cell and
+ * len all NULL with row_cap 0 stops there (sizing); otherwise DG_E_NOMEM when
+ * row_cap < *need and DG_E_INVALID when R * P reaches 2^32. val, cell and len
+ * (never NULL then) are column-major over row_cap, rows [0, R) of each column
+ * written; index (R entries) may be NULL. Offsets are relative to `thrift`. */
+int dg_rows_batch_host(dg_ctx *ctx, const dg_rows *rows, uint8_t root_type, const uint8_t *thrift,
+                       const uint64_t *in_off, uint64_t n, dg_rows_head *head, uint64_t *row_off, dg_row_ent *index,
+                       uint64_t *val, dg_col_cell *cell, uint32_t *len, uint64_t row_cap, uint64_t *need);
+
+/* ------------------------------------------------------------------------
  * ents: entry columns, the containers cols leaves out: GetByPath followed by
  * Node.List with String per element, Node.StrMap or Node.IntMap
  * (thrift/generic/cast.go:198-286), for a whole batch, as ragged columns. A

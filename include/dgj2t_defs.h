@@ -310,6 +310,24 @@ typedef struct dg_col_cell {
     uint32_t aux;   /* dg_tget_rec's aux; a list whose element type the cast rejects: that element type */
 } dg_col_cell; /* 8 bytes */
 
+/* rows (row columns, include/dgj2t.h dg_rows_*): the elements of a list or set
+ * as rows. A head's status is DG_TGET_OK / NOT_FOUND / E_READ / E_TYPE or
+ * DG_COL_E_UNSUPPORTED; a cell is a dg_col_cell (little-endian, no padding). */
+#define DG_ROWS_MAX_COLS 8u
+typedef struct dg_rows_head {
+    uint64_t first; /* OK: the arena offset of element 0 (the byte after the list header); else 0 */
+    uint32_t count; /* OK: the node's element count (Node.Len), the message's rows; else 0 */
+    uint8_t status;
+    uint8_t type;      /* OK: LIST or SET; DG_COL_E_UNSUPPORTED: the wire type found; else 0 */
+    uint8_t elem_type; /* OK: the element type, the root type of every row's lookup; else 0 */
+    uint8_t step;      /* a failed lookup: the failing step; otherwise the parent path's length */
+} dg_rows_head; /* 16 bytes */
+typedef struct dg_row_ent {
+    uint64_t off; /* the arena offset of the element's first byte */
+    uint32_t len; /* the element's byte length */
+    uint32_t msg; /* the message the row belongs to */
+} dg_row_ent; /* 16 bytes */
+
 /* ents (entry columns, include/dgj2t.h dg_ents_*): Node.List with String per
  * element, Node.StrMap and Node.IntMap as ragged columns. A kind is
  * DG_ENT_LISTSTR, or DG_ENT_STRMAP / DG_ENT_INTMAP with the value kind in its
