@@ -5,9 +5,9 @@
  * thrift/binary.go (DecodeBool 2152, DecodeByte, DecodeInt16/32/64,
  * DecodeDouble).
  *
- * The cell pass: one lane takes one (message, column) pair in tget_kernel's
- * geometry, runs tg_walk (tget_device.h, unchanged) and decodes at the found
- * position with ONE unaligned 8-byte load and a byte swap: every scalar, a
+ * The cell pass: one lane takes one (message, column) pair in tget's
+ * geometry (the pair pass, walk_kern.h), runs tg_walk (tget_device.h,
+ * unchanged) and decodes at the found position with ONE unaligned 8-byte load and a byte swap: every scalar, a
  * list's header (type byte + count) and a map's (two type bytes + count) lie
  * in those 8 bytes. The load starts at most at the message's end, so it stays
  * inside the 16 spare bytes tg_walk's windows already need.
@@ -17,12 +17,13 @@
  * contiguous bytes whatever the lists' lengths are.
  */
 #pragma once
+#include "scan_defs.h"
 #include "tget_device.h"
 
 namespace dg {
 
 constexpr uint32_t CL_BLOCK = 256;
-constexpr uint32_t CL_SCAN_TILE = 2048; /* counts per block of the scan */
+constexpr uint32_t CL_SCAN_TILE = SCAN_TILE; /* counts per block of the scan (vals and evals size their sums by this name) */
 constexpr uint32_t CL_EMIT_CHUNK = 8 * CL_BLOCK; /* elements a block of the emit takes a round */
 constexpr uint32_t CL_T_BOOL = 2, CL_T_DOUBLE = 4;
 

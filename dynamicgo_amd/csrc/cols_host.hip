@@ -6,18 +6,13 @@
 #include <string.h>
 
 #include "cols_device.h"
-#include "host_internal.h"
+#include "plan_internal.h"
 
 using namespace dg;
 
 static const uint64_t COLS_WS = (uint64_t)TG_DEEP_DEPTH * TG_DEEP_LANES * 8;
 
-static bool kind_is_list(uint32_t kind) { return (kind & DG_COL_LIST) != 0; }
-static bool kind_ok(uint32_t kind)
-{
-    return (kind >= DG_COL_BOOL && kind <= DG_COL_LEN) || kind == (DG_COL_LIST | DG_COL_INT) ||
-           kind == (DG_COL_LIST | DG_COL_F64);
-}
+static const PlanKinds COLS_KINDS{col_kind_ok, "cols", "paths", "kind"};
 
 /* one batch (device pointers) */
 struct ColsBatch {
@@ -29,10 +24,8 @@ struct ColsBatch {
     uint32_t *len;
 };
 
-/* the cell pass of one batch on stream s (ctx mutex held). The deep queue, its
- * two counters and the deep frames are the component's own, one per context:
- * a launch on another stream than the previous one waits for it, and a lookup
- * (tget_launch) on any stream shares nothing with it. */
+/* the cell pass of one batch on stream s (ctx mutex held), on the component's
+ * pass state */
 static int cols_launch(dg_ctx *c, const dg_cols *cp, uint8_t root_type, const ColsBatch &b, hipStream_t s)
 {
     const uint64_t n = b.n, P = cp->hdr.n_paths;
@@ -40,86 +33,67 @@ static int cols_launch(dg_ctx *c, const dg_cols *cp, uint8_t root_type, const Co
     if (!b.src || !b.in_off || !b.val || !b.cell) return set_err(DG_E_INVALID, "null buffer");
     if (((uintptr_t)b.val & 7) || ((uintptr_t)b.cell & 7) || ((uintptr_t)b.len & 3))
         return set_err(DG_E_INVALID, "values or cells not 8-byte aligned"); /* one store each */
-    bool wants_len = false;
-    uint64_t kinds = 0;
-    for (uint32_t k = 0; k < P; k++) {
-        wants_len |= cp->kinds[k] == DG_COL_STR || kind_is_list(cp->kinds[k]);
-        kinds |= (uint64_t)cp->kinds[k] << (k * 8);
-    }
-    if (wants_len && !b.len) return set_err(DG_E_INVALID, "a STR or list column needs d_len");
+    if (wants_len(cp->kinds, P) && !b.len) return set_err(DG_E_INVALID, "a STR or list column needs d_len");
     const uint64_t pairs = n * P;
     if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
         return set_err(DG_E_INVALID, "batch of %llu messages x %llu columns", (unsigned long long)n, (unsigned long long)P);
+    PassState &st = c->cols;
     int rc;
-    if (!c->cols.ws && ((rc = c->cols.ws.alloc(COLS_WS)) || (rc = c->cols_cnt.init(c->cols_cnt_buf, 1)))) return rc;
-    if ((rc = c->cols.grow(c->cols_list, pairs))) return rc; /* the previous launch may still fill the old list */
-    HIPCHK(c->cols.acquire(s));
+    if ((rc = st.first_use(COLS_WS, 1)) || (rc = st.room(pairs))) return rc;
     CLParams A;
     memset(&A, 0, sizeof A);
     A.tg.src = b.src, A.tg.in_off = b.in_off, A.tg.pairs = pairs, A.tg.P = (uint32_t)P, A.tg.root_type = root_type;
     A.tg.blob = cp->d_blob, A.tg.off_steps = cp->hdr.off_steps, A.tg.off_pool = cp->hdr.off_pool;
-    A.tg.deep_list = c->cols_list;
-    A.tg.deep_count = c->cols_cnt.mine(), A.tg.reset_count = c->cols_cnt.other();
-    A.tg.ws = (uint64_t *)(void *)c->cols.ws;
-    A.n = n, A.kinds = kinds;
+    A.tg.deep_list = st.list;
+    A.tg.ws = (uint64_t *)(void *)st.ws;
+    A.n = n, A.kinds = pack_kinds(cp->kinds, P);
     A.val = b.val, A.cell = (uint64_t *)(void *)b.cell, A.len = b.len;
-    launch_cols_pass(s, A);
-    const hipError_t e = hipGetLastError();
-    c->cols_cnt.finish(e == hipSuccess, s);
-    HIPCHK(c->cols.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "cols launch: %s", hipGetErrorString(e));
-    return DG_OK;
+    return st.enqueue(s, "cols", [&] {
+        return st.pass(s, [&](uint32_t *mine, uint32_t *other) {
+            A.tg.deep_count = mine, A.tg.reset_count = other;
+            launch_cols_pass(s, A);
+        });
+    });
 }
 
-/* list column k's scan and (with elems) emit on stream s (ctx mutex held); the
- * tile sums are shared like the deep queue */
-static int cols_list_launch(dg_ctx *c, const dg_cols *cp, uint32_t k, const uint8_t *src, uint64_t n,
-                            const uint64_t *val, const dg_col_cell *cell, const uint32_t *len, uint64_t *elem_off,
-                            uint64_t *elems, uint64_t cap, hipStream_t s)
+int dg_i_list_launch(dg_ctx *c, PassState &st, bool full_search, bool rows, const ListCol &l, hipStream_t s)
 {
-    if (k >= cp->hdr.n_paths || !kind_is_list(cp->kinds[k])) return set_err(DG_E_ARG, "column %u is no list column", k);
-    if (!elem_off) return set_err(DG_E_INVALID, "null buffer");
-    if (((uintptr_t)elem_off & 7) || ((uintptr_t)elems & 7)) return set_err(DG_E_INVALID, "offsets or elements not 8-byte aligned");
-    if (n > 0xFFFFFFFFull) return set_err(DG_E_INVALID, "batch of %llu messages", (unsigned long long)n);
+    const uint64_t n = l.n;
+    if (!l.elem_off) return set_err(DG_E_INVALID, "null buffer");
+    if (((uintptr_t)l.elem_off & 7) || ((uintptr_t)l.elems & 7)) return set_err(DG_E_INVALID, "offsets or elements not 8-byte aligned");
+    if (n > 0xFFFFFFFFull)
+        return rows ? set_err(DG_E_INVALID, "%llu rows", (unsigned long long)n)
+                    : set_err(DG_E_INVALID, "batch of %llu messages", (unsigned long long)n);
     if (n == 0) { /* the total, so that a reader of d_elem_off[n] finds 0 */
-        HIPCHK(hipMemsetAsync(elem_off, 0, 8, s));
+        HIPCHK(hipMemsetAsync(l.elem_off, 0, 8, s));
         return DG_OK;
     }
-    if (!src || !val || !cell || !len) return set_err(DG_E_INVALID, "null buffer");
-    if (int rc = c->cols.grow(c->cols_sums, (n + CL_SCAN_TILE - 1) / CL_SCAN_TILE)) return rc;
-    HIPCHK(c->cols.acquire(s));
-    launch_cols_scan(s, len, n, c->cols_sums, elem_off);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && elems && cap) {
-        const CLEmit E{src, n, val, (const uint64_t *)(const void *)cell, elem_off, elems, cap};
-        launch_cols_emit(s, E, (uint32_t)std::max(c->n_cu, 1) * 8u, c->knobs.cols_full_search == 1);
-        e = hipGetLastError();
-    }
-    HIPCHK(c->cols.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "cols list launch: %s", hipGetErrorString(e));
-    return DG_OK;
+    if (!l.src || !l.val || !l.cell || !l.len) return set_err(DG_E_INVALID, "null buffer");
+    if (int rc = st.grow(st.sums, (n + SCAN_TILE - 1) / SCAN_TILE)) return rc;
+    return st.enqueue(s, rows ? "rows list" : "cols list", [&] {
+        launch_cols_scan(s, l.len, n, st.sums, l.elem_off);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess && l.elems && l.cap) {
+            const CLEmit E{l.src, n, l.val, (const uint64_t *)(const void *)l.cell, l.elem_off, l.elems, l.cap};
+            launch_cols_emit(s, E, (uint32_t)std::max(c->n_cu, 1) * 8u, full_search);
+            e = hipGetLastError();
+        }
+        return e;
+    });
+}
+
+/* list column k of plan cp (see dg_i_list_launch) */
+static int cols_list_launch(dg_ctx *c, const dg_cols *cp, uint32_t k, const ListCol &l, hipStream_t s)
+{
+    if (k >= cp->hdr.n_paths || !kind_is_list(cp->kinds[k])) return set_err(DG_E_ARG, "column %u is no list column", k);
+    return dg_i_list_launch(c, c->cols, c->knobs.cols_full_search == 1, false, l, s);
 }
 
 extern "C" {
 
 int dg_cols_create(dg_ctx *c, const void *blob, size_t len, const uint8_t *kinds, uint32_t n_kinds, dg_cols **out)
 {
-    if (!c || !blob || !kinds || !out) return set_err(DG_E_INVALID, "null ctx/blob/kinds/out");
-    dg_path_hdr h;
-    if (int rc = dg_i_path_validate(blob, len, h)) return rc;
-    if (n_kinds != h.n_paths) return set_err(DG_E_ARG, "%u kinds for %u paths", n_kinds, h.n_paths);
-    for (uint32_t k = 0; k < n_kinds; k++)
-        if (!kind_ok(kinds[k])) return set_err(DG_E_ARG, "column %u: unknown kind %u", k, kinds[k]);
-    Entry g(c, true);
-    if (g.rc) return g.rc;
-    std::unique_ptr<dg_cols> cp(new dg_cols());
-    cp->ctx = c;
-    cp->hdr = h;
-    memset(cp->kinds, 0, sizeof cp->kinds);
-    memcpy(cp->kinds, kinds, n_kinds);
-    if (int rc = upload_blob(cp->d_blob, blob, h.total_len, "cols")) return rc;
-    *out = cp.release();
-    return DG_OK;
+    return plan_create(c, blob, len, kinds, n_kinds, COLS_KINDS, out);
 }
 
 void dg_cols_destroy(dg_cols *p) { destroy_with_blob(p); }
@@ -141,7 +115,7 @@ int dg_cols_list_device(dg_ctx *c, const dg_cols *cp, uint32_t k, const uint8_t 
 {
     Entry g(c, c && cp && cp->ctx == c, stream, "null ctx/columns, or columns of another context");
     if (g.rc) return g.rc;
-    return cols_list_launch(c, cp, k, d_thrift, n, d_val_k, d_cell_k, d_len_k, d_elem_off, d_elems, elem_cap, g.s);
+    return cols_list_launch(c, cp, k, ListCol{d_thrift, n, d_val_k, d_cell_k, d_len_k, d_elem_off, d_elems, elem_cap}, g.s);
 }
 
 int dg_cols_batch_host(dg_ctx *c, const dg_cols *cp, uint8_t root_type, const uint8_t *thrift, const uint64_t *in_off,
@@ -177,8 +151,8 @@ int dg_cols_batch_host(dg_ctx *c, const dg_cols *cp, uint8_t root_type, const ui
     if ((rc = cols_launch(c, cp, root_type, ColsBatch{c->d_json, c->d_in_off, n, d_val, d_cell, d_len}, s))) return rc;
     for (uint64_t j = 0; j < L && !rc; j++) { /* sizing */
         const uint64_t at = lists[j] * n;
-        rc = cols_list_launch(c, cp, lists[j], c->d_json, n, d_val + at, d_cell + at, d_len + at, c->d_ret + j * (n + 1),
-                              nullptr, 0, s);
+        rc = cols_list_launch(c, cp, lists[j],
+                              ListCol{c->d_json, n, d_val + at, d_cell + at, d_len + at, c->d_ret + j * (n + 1), nullptr, 0}, s);
     }
     if (rc || (rc = hb.copy(val, d_val, cells * 8, hipMemcpyDeviceToHost)) ||
         (rc = hb.copy(cell, d_cell, cells * 8, hipMemcpyDeviceToHost)) ||
@@ -190,12 +164,7 @@ int dg_cols_batch_host(dg_ctx *c, const dg_cols *cp, uint8_t root_type, const ui
         if (cp->kinds[k] == DG_COL_STR || kind_is_list(cp->kinds[k]))
             for (uint64_t i = k * n; i < (k + 1) * n; i++)
                 if (cell[i].status == DG_TGET_OK) val[i] += in_off[0];
-    std::vector<uint64_t> base(L + 1, 0); /* the columns' elements one after the other */
-    for (uint64_t j = 0; j < L; j++) {
-        uint64_t *eo = elem_off + j * (n + 1);
-        base[j + 1] = base[j] + eo[n];
-        for (uint64_t i = 0; i <= n; i++) eo[i] += base[j];
-    }
+    const std::vector<uint64_t> base = chain_columns(elem_off, L, n); /* the columns' elements one after the other */
     const uint64_t want = base[L];
     if (need) *need = want;
     if (!elems && !elem_cap) return DG_OK; /* sizing */
@@ -205,9 +174,8 @@ int dg_cols_batch_host(dg_ctx *c, const dg_cols *cp, uint8_t root_type, const ui
     uint64_t *d_elems = (uint64_t *)(void *)c->d_pack.p;
     for (uint64_t j = 0; j < L; j++) {
         const uint64_t at = lists[j] * n, cnt = base[j + 1] - base[j];
-        if (cnt && (rc = cols_list_launch(c, cp, lists[j], c->d_json, n, d_val + at, d_cell + at, d_len + at,
-                                          c->d_ret + j * (n + 1), d_elems + base[j], cnt, s)))
-            return rc;
+        const ListCol l{c->d_json, n, d_val + at, d_cell + at, d_len + at, c->d_ret + j * (n + 1), d_elems + base[j], cnt};
+        if (cnt && (rc = cols_list_launch(c, cp, lists[j], l, s))) return rc;
     }
     return hb.download(elems, c->d_pack, want * 8);
 }

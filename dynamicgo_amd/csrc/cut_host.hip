@@ -81,8 +81,8 @@ struct CutBatch {
 };
 
 /* one batch on stream s (ctx mutex held): the lane route over the whole batch,
- * then the wave route over what it queued, back to back. The queue and its two
- * counters are one per context, ordered across streams like tget's. */
+ * then the wave route over what it queued, back to back, on the component's
+ * pass state (a queue and its counters, no frames). */
 static int cut_launch(dg_ctx *c, const dg_cut *pl, uint64_t opts, const CutBatch &b, hipStream_t s)
 {
     const uint64_t n = b.n;
@@ -91,10 +91,9 @@ static int cut_launch(dg_ctx *c, const dg_cut *pl, uint64_t opts, const CutBatch
     if (n > 0xFFFFFFFFull) return set_err(DG_E_INVALID, "batch of %llu messages", (unsigned long long)n);
     if (opts & ~(DG_CUT_WRITE_DEFAULT | DG_CUT_DISALLOW_UNKNOWN | DG_CUT_NOT_CHECK_REQ))
         return set_err(DG_E_INVALID, "unknown cut option bits %llx", (unsigned long long)opts);
+    PassState &st = c->cut;
     int rc;
-    if (!c->cut_cnt_buf && (rc = c->cut_cnt.init(c->cut_cnt_buf, 1))) return rc;
-    if ((rc = c->cut.grow(c->cut_list, n))) return rc; /* the previous launch may still fill the old list */
-    HIPCHK(c->cut.acquire(s));
+    if ((rc = st.first_use(0, 1)) || (rc = st.room(n))) return rc;
     CutParams A;
     memset(&A, 0, sizeof A);
     const uint8_t *blob = pl->d_blob;
@@ -109,23 +108,19 @@ static int cut_launch(dg_ctx *c, const dg_cut *pl, uint64_t opts, const CutBatch
     A.src = b.src, A.in_off = b.in_off, A.n = n;
     A.out = b.out, A.out_off = b.out_off, A.out_len = b.out_len, A.ret = b.ret;
     A.wave_min = c->knobs.cut_wave_min < 0 ? 0 : (uint64_t)c->knobs.cut_wave_min;
-    A.wave_list = c->cut_list;
-    A.wave_count = c->cut_cnt.mine();
-    A.reset_count = c->cut_cnt.other();
+    A.wave_list = st.list;
     (void)b.max_len; /* a hint no route reads today: both kernels always run */
-    launch_cut_lane(s, A);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        /* a fixed grid striding over the queue, a wave per message: enough
-         * waves to fill the device, no more blocks than the batch could queue */
-        const uint64_t want = (n + CUT_WAVES - 1) / CUT_WAVES;
-        launch_cut_wave(s, A, (uint32_t)std::min<uint64_t>(want, (uint64_t)c->n_cu * 4));
-        e = hipGetLastError();
-    }
-    c->cut_cnt.finish(e == hipSuccess, s);
-    HIPCHK(c->cut.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "cut launch: %s", hipGetErrorString(e));
-    return DG_OK;
+    return st.enqueue(s, "cut", [&] {
+        return st.pass(s, [&](uint32_t *mine, uint32_t *other) {
+            A.wave_count = mine, A.reset_count = other;
+            launch_cut_lane(s, A);
+            if (hipPeekAtLastError() != hipSuccess) return;
+            /* a fixed grid striding over the queue, a wave per message: enough
+             * waves to fill the device, no more blocks than the batch could queue */
+            const uint64_t want = (n + CUT_WAVES - 1) / CUT_WAVES;
+            launch_cut_wave(s, A, (uint32_t)std::min<uint64_t>(want, (uint64_t)c->n_cu * 4));
+        });
+    });
 }
 
 extern "C" {

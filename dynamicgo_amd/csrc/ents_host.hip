@@ -6,13 +6,13 @@
 #include <string.h>
 
 #include "ents_device.h"
-#include "host_internal.h"
+#include "plan_internal.h"
 
 using namespace dg;
 
 static const uint64_t ENTS_WS = (uint64_t)TG_DEEP_DEPTH * TG_DEEP_LANES * 8;
 
-static bool kind_ok(uint32_t kind)
+static bool ent_kind_ok(uint32_t kind)
 {
     if (kind == DG_ENT_LISTSTR) return true;
     const uint32_t c = kind & ~15u, v = kind & 15u;
@@ -21,6 +21,8 @@ static bool kind_ok(uint32_t kind)
 }
 static bool kind_str_key(uint32_t kind) { return (kind & DG_ENT_STRMAP) != 0; }
 static bool kind_str_val(uint32_t kind) { return kind == DG_ENT_LISTSTR || (kind & 15u) == DG_ENT_STR; }
+
+static const PlanKinds ENTS_KINDS{ent_kind_ok, "ents", "paths", "entry kind"};
 
 /* one batch (device pointers) */
 struct EntsBatch {
@@ -44,10 +46,8 @@ struct EntsEmit {
     uint64_t cap;
 };
 
-/* the cell pass of one batch on stream s (ctx mutex held). The deep queue, its
- * two counters and the deep frames are the component's own, one per context:
- * a launch on another stream than the previous one waits for it, and a lookup
- * or a cols call on any stream shares nothing with it. */
+/* the cell pass of one batch on stream s (ctx mutex held), on the component's
+ * pass state */
 static int ents_launch(dg_ctx *c, const dg_ents *ep, uint8_t root_type, const EntsBatch &b, hipStream_t s)
 {
     const uint64_t n = b.n, P = ep->hdr.n_paths;
@@ -55,34 +55,30 @@ static int ents_launch(dg_ctx *c, const dg_ents *ep, uint8_t root_type, const En
     if (!b.src || !b.in_off || !b.val || !b.cell || !b.len || !b.span) return set_err(DG_E_INVALID, "null buffer");
     if (((uintptr_t)b.val & 7) || ((uintptr_t)b.cell & 7) || ((uintptr_t)b.len & 3) || ((uintptr_t)b.span & 3))
         return set_err(DG_E_INVALID, "values or cells not 8-byte aligned"); /* one store each */
-    uint64_t kinds = 0;
-    for (uint32_t k = 0; k < P; k++) kinds |= (uint64_t)ep->kinds[k] << (k * 8);
     const uint64_t pairs = n * P;
     if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
         return set_err(DG_E_INVALID, "batch of %llu messages x %llu columns", (unsigned long long)n, (unsigned long long)P);
+    PassState &st = c->ents;
     int rc;
-    if (!c->ents.ws && ((rc = c->ents.ws.alloc(ENTS_WS)) || (rc = c->ents_cnt.init(c->ents_cnt_buf, 1)))) return rc;
-    if ((rc = c->ents.grow(c->ents_list, pairs))) return rc; /* the previous launch may still fill the old list */
-    HIPCHK(c->ents.acquire(s));
+    if ((rc = st.first_use(ENTS_WS, 1)) || (rc = st.room(pairs))) return rc;
     ENParams A;
     memset(&A, 0, sizeof A);
     A.tg.src = b.src, A.tg.in_off = b.in_off, A.tg.pairs = pairs, A.tg.P = (uint32_t)P, A.tg.root_type = root_type;
     A.tg.blob = ep->d_blob, A.tg.off_steps = ep->hdr.off_steps, A.tg.off_pool = ep->hdr.off_pool;
-    A.tg.deep_list = c->ents_list;
-    A.tg.deep_count = c->ents_cnt.mine(), A.tg.reset_count = c->ents_cnt.other();
-    A.tg.ws = (uint64_t *)(void *)c->ents.ws;
-    A.n = n, A.kinds = kinds;
+    A.tg.deep_list = st.list;
+    A.tg.ws = (uint64_t *)(void *)st.ws;
+    A.n = n, A.kinds = pack_kinds(ep->kinds, P);
     A.val = b.val, A.cell = (uint64_t *)(void *)b.cell, A.len = b.len, A.span = b.span;
-    launch_ents_pass(s, A);
-    const hipError_t e = hipGetLastError();
-    c->ents_cnt.finish(e == hipSuccess, s);
-    HIPCHK(c->ents.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "ents launch: %s", hipGetErrorString(e));
-    return DG_OK;
+    return st.enqueue(s, "ents", [&] {
+        return st.pass(s, [&](uint32_t *mine, uint32_t *other) {
+            A.tg.deep_count = mine, A.tg.reset_count = other;
+            launch_ents_pass(s, A);
+        });
+    });
 }
 
 /* column k's scan and (with an output array and a capacity) emit on stream s
- * (ctx mutex held); the tile sums are shared like the deep queue */
+ * (ctx mutex held); the tile sums are the pass state's */
 static int ents_emit_launch(dg_ctx *c, const dg_ents *ep, uint32_t k, const uint8_t *src, uint64_t n, const EntsEmit &o,
                             hipStream_t s)
 {
@@ -97,55 +93,31 @@ static int ents_emit_launch(dg_ctx *c, const dg_ents *ep, uint32_t k, const uint
         return DG_OK;
     }
     if (!src || !o.val || !o.cell || !o.len || !o.span) return set_err(DG_E_INVALID, "null buffer");
-    if (int rc = c->ents.grow(c->ents_sums, (n + CL_SCAN_TILE - 1) / CL_SCAN_TILE)) return rc;
-    HIPCHK(c->ents.acquire(s));
-    launch_cols_scan(s, o.len, n, c->ents_sums, o.off);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && (o.key || o.klen || o.v || o.vlen) && o.cap) {
-        /* an array the kind has nothing for is not touched */
-        const uint32_t kind = ep->kinds[k];
-        const ENEmit E{src,
-                       n,
-                       o.val,
-                       (const uint64_t *)(const void *)o.cell,
-                       o.len,
-                       o.span,
-                       o.off,
-                       kind == DG_ENT_LISTSTR ? nullptr : o.key,
-                       kind_str_key(kind) ? o.klen : nullptr,
-                       o.v,
-                       kind_str_val(kind) ? o.vlen : nullptr,
-                       o.cap,
-                       kind};
-        const int64_t st = c->knobs.ents_stage;
-        launch_ents_emit(s, E, (uint32_t)std::max(c->n_cu, 1) * 8u, st == 4 || st == 8 || st == 16 ? (uint32_t)st : 0u);
-        e = hipGetLastError();
-    }
-    HIPCHK(c->ents.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "ents emit launch: %s", hipGetErrorString(e));
-    return DG_OK;
+    PassState &st = c->ents;
+    if (int rc = st.grow(st.sums, (n + SCAN_TILE - 1) / SCAN_TILE)) return rc;
+    return st.enqueue(s, "ents emit", [&] {
+        launch_cols_scan(s, o.len, n, st.sums, o.off);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess && (o.key || o.klen || o.v || o.vlen) && o.cap) {
+            /* an array the kind has nothing for is not touched */
+            const uint32_t kind = ep->kinds[k];
+            const ENEmit E{src, n, o.val, (const uint64_t *)(const void *)o.cell, o.len, o.span, o.off,
+                           kind == DG_ENT_LISTSTR ? nullptr : o.key, kind_str_key(kind) ? o.klen : nullptr, o.v,
+                           kind_str_val(kind) ? o.vlen : nullptr, o.cap, kind};
+            const int64_t stage = c->knobs.ents_stage;
+            launch_ents_emit(s, E, (uint32_t)std::max(c->n_cu, 1) * 8u,
+                             stage == 4 || stage == 8 || stage == 16 ? (uint32_t)stage : 0u);
+            e = hipGetLastError();
+        }
+        return e;
+    });
 }
 
 extern "C" {
 
 int dg_ents_create(dg_ctx *c, const void *blob, size_t len, const uint8_t *kinds, uint32_t n_kinds, dg_ents **out)
 {
-    if (!c || !blob || !kinds || !out) return set_err(DG_E_INVALID, "null ctx/blob/kinds/out");
-    dg_path_hdr h;
-    if (int rc = dg_i_path_validate(blob, len, h)) return rc;
-    if (n_kinds != h.n_paths) return set_err(DG_E_ARG, "%u kinds for %u paths", n_kinds, h.n_paths);
-    for (uint32_t k = 0; k < n_kinds; k++)
-        if (!kind_ok(kinds[k])) return set_err(DG_E_ARG, "column %u: unknown entry kind %u", k, kinds[k]);
-    Entry g(c, true);
-    if (g.rc) return g.rc;
-    std::unique_ptr<dg_ents> ep(new dg_ents());
-    ep->ctx = c;
-    ep->hdr = h;
-    memset(ep->kinds, 0, sizeof ep->kinds);
-    memcpy(ep->kinds, kinds, n_kinds);
-    if (int rc = upload_blob(ep->d_blob, blob, h.total_len, "ents")) return rc;
-    *out = ep.release();
-    return DG_OK;
+    return plan_create(c, blob, len, kinds, n_kinds, ENTS_KINDS, out);
 }
 
 void dg_ents_destroy(dg_ents *p) { destroy_with_blob(p); }
@@ -214,12 +186,7 @@ int dg_ents_batch_host(dg_ctx *c, const dg_ents *ep, uint8_t root_type, const ui
     /* offsets relative to the caller's arena: the upload began at in_off[0] */
     for (uint64_t i = 0; i < cells; i++)
         if (cell[i].status == DG_TGET_OK) val[i] += in_off[0];
-    std::vector<uint64_t> base(P + 1, 0); /* the columns' entries one after the other */
-    for (uint64_t k = 0; k < P; k++) {
-        uint64_t *eo = ent_off + k * (n + 1);
-        base[k + 1] = base[k] + eo[n];
-        for (uint64_t i = 0; i <= n; i++) eo[i] += base[k];
-    }
+    const std::vector<uint64_t> base = chain_columns(ent_off, P, n); /* the columns' entries one after the other */
     const uint64_t want = base[P];
     if (need) *need = want;
     const bool any = key || key_len || ent_val || ent_val_len;

@@ -1,7 +1,8 @@
-/* ents kernels (entry columns, ents_device.h): the cell pass with its deep pass,
+/* ents kernels (entry columns, ents_device.h): the cell pass (walk_kern.h),
  * the fixed-stride emit and the two shapes of the variable-stride emit. The
  * scan of the counts is cols' (launch_cols_scan). */
 #include "ents_device.h"
+#include "walk_kern.h"
 
 namespace dg {
 
@@ -15,44 +16,32 @@ static __device__ __forceinline__ void en_store(const ENParams &A, uint64_t i, u
     A.span[at] = c.span;
 }
 
-/* cols_kernel's geometry: one lane per (message, column) pair, the P pairs of
- * a message in neighbouring lanes; pairs whose skip nests beyond the LDS
- * frames are queued for ents_deep_kernel */
-__global__ __launch_bounds__(TG_BLOCK) void ents_kernel(ENParams A)
-{
-    __shared__ uint64_t lf[TG_LDS_DEPTH * TG_BLOCK];
-    const uint64_t q = (uint64_t)blockIdx.x * TG_BLOCK + threadIdx.x;
-    if (q >= A.tg.pairs) return;
-    const uint64_t i = q / A.tg.P;
-    const uint32_t k = (uint32_t)(q - i * A.tg.P);
-    const uint64_t a = A.tg.in_off[i], e = A.tg.in_off[i + 1];
-    const TGLdsFrames fr{&lf[threadIdx.x]};
-    const TGRes r = tg_walk(A.tg, A.tg.src + a, e - a, k, fr);
-    if (r.status == TG_ST_DEEP) {
-        A.tg.deep_list[atomicAdd(A.tg.deep_count, 1u)] = (uint32_t)q;
-        return;
-    }
-    en_store(A, i, k, en_cell((uint32_t)(A.kinds >> (k * 8)) & 0xFFu, r, A.tg.src + a, a));
-}
-
-/* the queued pairs again with TG_DEEP_DEPTH frames per lane in device memory;
- * also zeroes the counter the previous launch used */
-__global__ __launch_bounds__(TG_DEEP_BLOCK) void ents_deep_kernel(ENParams A)
-{
-    const uint32_t cnt = *(volatile const uint32_t *)A.tg.deep_count;
-    const uint32_t lane = blockIdx.x * TG_DEEP_BLOCK + threadIdx.x;
-    if (lane == 0) *A.tg.reset_count = 0;
-    const TGDeepFrames fr{A.tg.ws + lane};
-    for (uint32_t g = lane; g < cnt; g += TG_DEEP_LANES) {
-        const uint64_t q = A.tg.deep_list[g];
+/* Pair q = (message q / P, column q % P) of the pair pass (walk_kern.h), as cols' */
+struct EntsOp {
+    using Params = ENParams;
+    using Lds = TGLdsFrames;
+    using Deep = TGDeepFrames;
+    static __device__ __forceinline__ uint64_t pairs(const ENParams &A) { return A.tg.pairs; }
+    static __device__ __forceinline__ WalkQueue queue(const ENParams &A) { return walk_queue(A.tg); }
+    template <class FR>
+    static __device__ __forceinline__ bool pair(const ENParams &A, uint64_t q, const FR &fr, bool last)
+    {
         const uint64_t i = q / A.tg.P;
         const uint32_t k = (uint32_t)(q - i * A.tg.P);
         const uint64_t a = A.tg.in_off[i], e = A.tg.in_off[i + 1];
         TGRes r = tg_walk(A.tg, A.tg.src + a, e - a, k, fr);
-        if (r.status == TG_ST_DEEP) r = tg_res(DG_TGET_E_READ, r.step); /* unreachable: 1023 levels fit */
+        if (r.status == TG_ST_DEEP) {
+            if (!last) return true;
+            r = tg_res(DG_TGET_E_READ, r.step); /* unreachable: 1023 levels fit */
+        }
         en_store(A, i, k, en_cell((uint32_t)(A.kinds >> (k * 8)) & 0xFFu, r, A.tg.src + a, a));
+        return false;
     }
-}
+    template <class FR>
+    static __device__ __forceinline__ bool lane(const ENParams &A, uint64_t q, const FR &fr) { return pair(A, q, fr, false); }
+    template <class FR>
+    static __device__ __forceinline__ bool deep(const ENParams &A, uint64_t q, const FR &fr) { return pair(A, q, fr, true); }
+};
 
 /* The fixed-stride emit, in the shape of cols_emit_kernel: a block takes a
  * chunk of EN_EMIT_CHUNK neighbouring entries a round; its first and last lane
@@ -166,12 +155,7 @@ __global__ __launch_bounds__(EN_WAVE) void ents_emit_stage_kernel(ENEmit E)
     }
 }
 
-void launch_ents_pass(hipStream_t s, const ENParams &A)
-{
-    const dim3 grid((uint32_t)((A.tg.pairs + TG_BLOCK - 1) / TG_BLOCK)), block(TG_BLOCK);
-    hipLaunchKernelGGL(ents_kernel, grid, block, 0, s, A);
-    hipLaunchKernelGGL(ents_deep_kernel, dim3(TG_DEEP_BLOCKS), dim3(TG_DEEP_BLOCK), 0, s, A);
-}
+void launch_ents_pass(hipStream_t s, const ENParams &A) { launch_walk<EntsOp>(s, A, A.tg.pairs); }
 
 void launch_ents_emit(hipStream_t s, const ENEmit &E, uint32_t max_blocks, uint32_t stage)
 {

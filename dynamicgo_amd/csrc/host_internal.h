@@ -1,18 +1,21 @@
 /*
- * host_internal.h — what the C-ABI translation units share: the owners of
- * GPU resources (device and pinned arrays, events, streams), the rule that
- * orders a shared buffer across streams, the context, descriptor and
- * per-stream scratch records, the entry guard, the argument records of one
- * batch, the host batch of the thrift/generic and t2j entries (HostBatch) and the
- * error helpers (j2t_host.hip defines the functions; t2j_host,
- * tget_host, cut_host, editm_host, kids_host, cols_host, ents_host, rows_host, vals_host, evals_host and j2t_pipe
- * use them).
+ * host_internal.h — what the C-ABI translation units share: the owners of GPU
+ * resources (device and pinned arrays, events, streams), the rule that orders a
+ * shared buffer across streams, the pass state of the components that queue
+ * work for a second pass (PassState: tget, cut, kids, cols, ents, rows), the
+ * context, descriptor, plan and per-stream scratch records, the entry guard,
+ * the argument records of one batch, the host batch of the thrift/generic and
+ * t2j entries (HostBatch) and the error helpers (j2t_host.hip defines the
+ * functions; t2j_host, tget_host, cut_host, editm_host, kids_host, cols_host,
+ * ents_host, rows_host, vals_host, evals_host and j2t_pipe use them). What only
+ * cols, ents and rows share is in plan_internal.h.
  */
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <memory>
@@ -164,7 +167,7 @@ struct StreamOrder {
 };
 
 /* one workspace per context, shared across streams (t2j's deep frames and
- * token regions, tget's frames); ws is freed before done is destroyed */
+ * token regions); ws is freed before done is destroyed */
 struct SharedWs : StreamOrder {
     DevArr<uint8_t> ws;
 };
@@ -181,7 +184,8 @@ struct AltCounters {
     /* first use: the two sets, `words` counters each, in buf, zeroed */
     int init(DevArr<uint32_t> &buf, uint32_t words)
     {
-        if (int rc = buf.alloc(4)) return rc;
+        if (!buf)
+            if (int rc = buf.alloc(4)) return rc;
         HIPCHK(hipMemset(buf, 0, 16));
         HIPCHK(hipDeviceSynchronize()); /* before a non-blocking stream counts on it */
         set[0] = buf, set[1] = buf + words, bytes = 4 * words;
@@ -192,6 +196,55 @@ struct AltCounters {
         if (ok) cur ^= 1u;
         else
             for (uint32_t *p : set) (void)hipMemsetAsync(p, 0, bytes, s);
+    }
+};
+
+/* What a component whose lane pass queues work for a second pass keeps per
+ * context (tget, cut, kids, cols, ents, rows): the deep frames (cut has none),
+ * the queue, the two alternating counter sets and the scan's tile sums (where
+ * it scans). One per context and shared by every stream, so it is ordered
+ * like a workspace: a launch on another stream than the previous one waits
+ * for it. The buffers are freed before `done` is destroyed. */
+struct PassState : StreamOrder {
+    DevArr<uint8_t> ws;
+    DevArr<uint32_t> list, cnt_buf;
+    AltCounters cnt;
+    DevArr<uint64_t> sums;
+    /* first use: ws_bytes of frames (0: none) and the counters, `words` a set */
+    int first_use(uint64_t ws_bytes, uint32_t words)
+    {
+        if (cnt.set[0]) return DG_OK; /* set by a complete init: a first use that failed half way is taken up again */
+        if (ws_bytes && !ws)
+            if (int rc = ws.alloc(ws_bytes)) return rc;
+        return cnt.init(cnt_buf, words);
+    }
+    /* room for `queue` entries and `tiles` tile sums (grow waits for the previous launch) */
+    int room(uint64_t queue, uint64_t tiles = 0)
+    {
+        if (int rc = grow(list, queue)) return rc;
+        return grow(sums, tiles);
+    }
+    /* One enqueue on stream s: acquire, the caller's launches (they answer the
+     * first launch error), publish -- also after a failed enqueue, and before
+     * its error is returned -- and the error as "<what> launch: ...". */
+    template <class F>
+    int enqueue(hipStream_t s, const char *what, F launches)
+    {
+        HIPCHK(acquire(s));
+        const hipError_t e = launches();
+        HIPCHK(publish(s));
+        if (e != hipSuccess) return set_err(DG_E_HIP, "%s launch: %s", what, hipGetErrorString(e));
+        return DG_OK;
+    }
+    /* inside enqueue: one lane pass with its second pass, launch(mine, other), on the counter set whose turn it
+     * is; a launch of two steps leaves the second out when hipPeekAtLastError shows the first failed */
+    template <class F>
+    hipError_t pass(hipStream_t s, F launch)
+    {
+        launch(cnt.mine(), cnt.other());
+        const hipError_t e = hipGetLastError();
+        cnt.finish(e == hipSuccess, s);
+        return e;
     }
 };
 
@@ -295,8 +348,9 @@ struct PipeBufDelete {
  * chunks (each synchronises its own stream, then frees) and its staging, the
  * scratches (before any stream they were last used on: an event last recorded
  * on a destroyed stream is not safe to wait on), the staging buffers, the
- * shared workspaces, the in-flight side streams and their events, and the
- * context's own stream last. */
+ * shared workspaces and the components' pass states (each frees its buffers
+ * before its own event), the in-flight side streams and their events, and
+ * the context's own stream last. */
 struct dg_ctx {
     int device = 0;
     Stream stream;
@@ -313,56 +367,35 @@ struct dg_ctx {
     Event fork_ev;
     std::vector<Event> side_ev;
     std::vector<Stream> side;
-    /* tget (tget_host.hip): the deep pass's frames (32 MB, allocated by the
-     * first lookup), its queue and the two alternating queue counters */
-    SharedWs tget;
-    DevArr<uint32_t> tget_list, tget_cnt_buf;
-    AltCounters tget_cnt;
-    /* cut (cut_host.hip): the wave route's queue and its two alternating
-     * counters, one per context like tget's */
-    StreamOrder cut;
-    DevArr<uint32_t> cut_list, cut_cnt_buf;
-    AltCounters cut_cnt;
+    /* The components' pass states (PassState: deep frames of 32 MB allocated by
+     * the first call, queue, two alternating counter sets, tile sums), one
+     * each, so that a call of one component on any stream shares nothing with
+     * a call of another. tget (tget_host.hip): no sums. */
+    PassState tget;
+    /* cut (cut_host.hip): the wave route's queue; no frames and no sums */
+    PassState cut;
     /* edit and editm (editm_host.hip): the lookup's (K + 1) n records of one
-     * batch, ordered across streams like tget's workspace */
+     * batch, ordered across streams like a pass state */
     StreamOrder edit;
     DevArr<dg_tget_rec> edit_rec;
     uint64_t edit_rec_n = 0, edit_rec_k = 0; /* messages and items of the launch that filled edit_rec */
-    /* kids (kids_host.hip): the deep pass's frames (32 MB, allocated by the
-     * first call), the deep and wide queues (n entries each), the two
-     * alternating counter sets {deep, wide} and the scan's tile sums */
-    SharedWs kids;
-    DevArr<uint32_t> kids_list, kids_cnt_buf;
-    AltCounters kids_cnt;
-    DevArr<uint64_t> kids_sums;
-    /* cols (cols_host.hip): the cell pass's deep frames (32 MB, allocated by
-     * the first call), its queue and two alternating queue counters, and the
-     * list scan's tile sums: its own, so that a lookup on another stream shares
-     * nothing with it */
-    SharedWs cols;
-    DevArr<uint32_t> cols_list, cols_cnt_buf;
-    AltCounters cols_cnt;
-    DevArr<uint64_t> cols_sums;
+    /* kids (kids_host.hip): the queue holds the deep and the wide queue (n
+     * entries each), a counter set is {deep, wide} */
+    PassState kids;
+    /* cols (cols_host.hip) */
+    PassState cols;
     /* vals (vals_host.hip): the size pass's lengths (n * K) and the scan's tile
      * sums: its own, ordered across streams */
     StreamOrder vals;
     DevArr<uint32_t> vals_len;
     DevArr<uint64_t> vals_sums;
-    /* ents (ents_host.hip): the cell pass's deep frames (32 MB, allocated by the
-     * first call), its queue, two alternating queue counters and the scan's
-     * tile sums: its own, like cols' */
-    SharedWs ents;
-    DevArr<uint32_t> ents_list, ents_cnt_buf;
-    AltCounters ents_cnt;
-    DevArr<uint64_t> ents_sums;
-    /* rows (rows_host.hip): the deep frames of its three lane passes (32 MB,
-     * allocated by the first call), their queue, two alternating queue
-     * counters, the heads' counts (n) and the scan's tile sums, and the row
-     * index of a call that gives none: its own, like cols' */
-    SharedWs rows;
-    DevArr<uint32_t> rows_list, rows_cnt_buf, rows_counts;
-    AltCounters rows_cnt;
-    DevArr<uint64_t> rows_sums;
+    /* ents (ents_host.hip) */
+    PassState ents;
+    /* rows (rows_host.hip): its three lane passes share the state; beside it
+     * the heads' counts (n) and the row index of a call that gives none,
+     * ordered by it */
+    PassState rows;
+    DevArr<uint32_t> rows_counts;
     DevArr<dg_row_ent> rows_index;
     /* the t2j wave kernel's token regions (t2j_wave_ws_bytes, ~200 MB) */
     SharedWs t2j_tok;
@@ -438,29 +471,25 @@ struct dg_path {
     dg_path_hdr hdr;
 };
 
-/* a column plan on its context's device (cols_host.hip): a path set and one kind per path */
-struct dg_cols {
+/* a plan of typed columns on its context's device: a path set and one kind
+ * per path. The column plan (cols_host.hip, DG_COL_* kinds) and the
+ * entry-column plan (ents_host.hip, DG_ENT_* kinds) are this record; the
+ * opaque types of the C header stay distinct. */
+struct PlanRec {
     dg_ctx *ctx;
     DevArr<uint8_t> d_blob;
     dg_path_hdr hdr;
     uint8_t kinds[DG_TGET_MAX_PATHS];
 };
+struct dg_cols : PlanRec {};
+struct dg_ents : PlanRec {};
 
-/* an entry-column plan (ents_host.hip): a path set and one DG_ENT_* kind per path */
-struct dg_ents {
-    dg_ctx *ctx;
-    DevArr<uint8_t> d_blob;
-    dg_path_hdr hdr;
-    uint8_t kinds[DG_TGET_MAX_PATHS];
-};
-
-/* a row-column plan (rows_host.hip): the parent's path set of one path, the
- * sub-paths' set and one DG_COL_* kind per sub-path */
-struct dg_rows {
-    dg_ctx *ctx;
-    DevArr<uint8_t> d_blob, d_sub;
-    dg_path_hdr hdr, sub_hdr;
-    uint8_t kinds[DG_ROWS_MAX_COLS];
+/* a row-column plan (rows_host.hip): the parent's path set of one path
+ * (d_blob, hdr), the sub-paths' set and one DG_COL_* kind per sub-path */
+static_assert(DG_ROWS_MAX_COLS == DG_TGET_MAX_PATHS, "a kind per sub-path");
+struct dg_rows : PlanRec {
+    DevArr<uint8_t> d_sub;
+    dg_path_hdr sub_hdr;
 };
 
 /* a value plan (vals_host.hip): K kinds and, in struct mode, K field ids */
@@ -729,14 +758,18 @@ inline int upload_blob(DevArr<uint8_t> &d, const void *blob, size_t len, const c
     return DG_OK;
 }
 
-/* the end of a dg_path or dg_cut: its blob goes under the context lock, on its device */
+/* the end of a plan (dg_path, dg_cut, dg_cols, dg_ents, dg_rows): its blobs go
+ * under the context lock, on its device */
+inline void reset_blobs(dg_rows &p) { p.d_blob.reset(), p.d_sub.reset(); }
+template <class P>
+void reset_blobs(P &p) { p.d_blob.reset(); }
 template <class P>
 void destroy_with_blob(P *p)
 {
     if (!p) return;
     {
         Entry g(p->ctx, true);
-        p->d_blob.reset();
+        reset_blobs(*p);
     }
     delete p;
 }

@@ -31,6 +31,7 @@
  * The storing sink never writes a record at or past the message's count.
  */
 #pragma once
+#include "scan_defs.h"
 #include "tget_device.h"
 
 namespace dg {
@@ -40,7 +41,6 @@ constexpr uint32_t KD_LDS_DEPTH = 8;     /* levels per lane in LDS: 2 words each
 constexpr uint32_t KD_DEEP_DEPTH = 1024; /* ... per lane of the deep pass */
 constexpr uint32_t KD_DEEP_BLOCK = 64, KD_DEEP_BLOCKS = 32;
 constexpr uint32_t KD_DEEP_LANES = KD_DEEP_BLOCK * KD_DEEP_BLOCKS;
-constexpr uint32_t KD_SCAN_TILE = 2048;  /* counts a block of the scan takes: 8 a lane */
 constexpr uint32_t KD_WIDE_BLOCK = 256;
 
 struct KDParams {

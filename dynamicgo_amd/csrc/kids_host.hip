@@ -24,10 +24,8 @@ struct KidsBatch {
 };
 
 /* one batch on stream s (ctx mutex held): count pass -> scan -> emit pass,
- * each pass followed by its deep pass, the emit pass by the wide kernel. The
- * queues, the two counter sets (alternating per pass; a deep pass zeroes the
- * other set), the tile sums and the deep frames are one per context: a launch
- * on another stream than the previous one waits for it. */
+ * each pass followed by its deep pass, the emit pass by the wide kernel, on the
+ * component's pass state (the counter sets alternate per pass). */
 static int kids_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t flags, const KidsBatch &b, hipStream_t s)
 {
     const uint64_t n = b.n;
@@ -37,12 +35,10 @@ static int kids_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t
         return set_err(DG_E_INVALID, "heads or records not 16-byte aligned"); /* 16-byte stores */
     if (n > 0xFFFFFFFFull) return set_err(DG_E_INVALID, "batch of %llu messages", (unsigned long long)n);
     if (flags & ~(DG_KIDS_F_RECURSE | DG_KIDS_F_COUNTED)) return set_err(DG_E_INVALID, "unknown flags %x", flags);
+    PassState &st = c->kids;
     int rc;
-    if (!c->kids.ws && ((rc = c->kids.ws.alloc(KIDS_WS)) || (rc = c->kids_cnt.init(c->kids_cnt_buf, 2)))) return rc;
-    /* the previous launch may still use the old queues and tile sums */
-    if ((rc = c->kids.grow(c->kids_list, 2 * n)) || (rc = c->kids.grow(c->kids_sums, (n + KD_SCAN_TILE - 1) / KD_SCAN_TILE)))
-        return rc;
-    HIPCHK(c->kids.acquire(s));
+    /* the queue: the deep and the wide one; a counter set: {deep, wide} */
+    if ((rc = st.first_use(KIDS_WS, 2)) || (rc = st.room(2 * n, (n + SCAN_TILE - 1) / SCAN_TILE))) return rc;
     KDParams A;
     memset(&A, 0, sizeof A);
     A.tg.src = b.src, A.tg.in_off = b.in_off, A.tg.root_type = root_type;
@@ -52,29 +48,28 @@ static int kids_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, uint32_t
     A.recurse = flags & DG_KIDS_F_RECURSE ? 1u : 0u;
     A.head = b.head, A.rec_off = b.rec_off, A.recs = b.recs, A.rec_cap = b.rec_cap;
     A.wide_min = c->knobs.kids_wide_min < 0 ? 0 : (uint64_t)c->knobs.kids_wide_min;
-    A.deep_list = c->kids_list, A.wide_list = c->kids_list + n;
-    A.ws = (uint64_t *)(void *)c->kids.ws;
+    A.deep_list = st.list, A.wide_list = st.list + n;
+    A.ws = (uint64_t *)(void *)st.ws;
     A.stats = c->d_stats;
-    hipError_t e = hipSuccess;
-    if (!(flags & DG_KIDS_F_COUNTED)) {
-        A.cnt = c->kids_cnt.mine(), A.reset = c->kids_cnt.other();
-        launch_kids_count(s, A);
-        e = hipGetLastError();
-        c->kids_cnt.finish(e == hipSuccess, s);
-        if (e == hipSuccess && c->knobs.kids_no_scan != 1) { /* the knob: time the count pass alone */
-            launch_kids_scan(s, A, c->kids_sums);
-            e = hipGetLastError();
+    return st.enqueue(s, "kids", [&] {
+        hipError_t e = hipSuccess;
+        if (!(flags & DG_KIDS_F_COUNTED)) {
+            e = st.pass(s, [&](uint32_t *mine, uint32_t *other) {
+                A.cnt = mine, A.reset = other;
+                launch_kids_count(s, A);
+            });
+            if (e == hipSuccess && c->knobs.kids_no_scan != 1) { /* the knob: time the count pass alone */
+                launch_kids_scan(s, A, st.sums);
+                e = hipGetLastError();
+            }
         }
-    }
-    if (e == hipSuccess && b.recs) {
-        A.cnt = c->kids_cnt.mine(), A.reset = c->kids_cnt.other();
-        launch_kids_emit(s, A, (uint32_t)std::max(c->n_cu, 1) * 4u);
-        e = hipGetLastError();
-        c->kids_cnt.finish(e == hipSuccess, s);
-    }
-    HIPCHK(c->kids.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "kids launch: %s", hipGetErrorString(e));
-    return DG_OK;
+        if (e == hipSuccess && b.recs)
+            e = st.pass(s, [&](uint32_t *mine, uint32_t *other) {
+                A.cnt = mine, A.reset = other;
+                launch_kids_emit(s, A, (uint32_t)std::max(c->n_cu, 1) * 4u);
+            });
+        return e;
+    });
 }
 
 static int kids_args(const dg_ctx *c, const dg_path *ps)

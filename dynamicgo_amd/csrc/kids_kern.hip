@@ -1,6 +1,7 @@
 /* kids kernels (batched Children, kids_device.h): the count and emit passes with
- * their deep passes, the scan of the counts and the wide emit. */
+ * their deep passes, the scan of the counts (scan_kern.h) and the wide emit. */
 #include "kids_device.h"
+#include "scan_kern.h"
 
 namespace dg {
 
@@ -112,95 +113,16 @@ __global__ __launch_bounds__(KD_WIDE_BLOCK) void kids_wide_kernel(KDParams A)
     }
 }
 
-/* ---- the scan: rec_off[i] = the sum of head[0..i).count as 64-bit, rec_off[n]
- * the total. Three small kernels over tiles of KD_SCAN_TILE counts: tile sums,
- * their exclusive scan by one block, then every tile's own scan on top of its
- * base. Any n below 2^32: the tile sums are scanned in a loop with a carry. */
-static __device__ __forceinline__ uint64_t kd_block_scan(uint64_t v, uint64_t *sh, uint64_t &total)
-{
-    const uint32_t t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < KD_BLOCK; d <<= 1) {
-        const uint64_t x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    const uint64_t incl = sh[t];
-    total = sh[KD_BLOCK - 1];
-    __syncthreads();
-    return incl - v; /* exclusive */
-}
-
-__global__ __launch_bounds__(KD_BLOCK) void kids_scan_sums_kernel(const dg_kids_head *head, uint64_t n, uint64_t *sums)
-{
-    __shared__ uint64_t sh[KD_BLOCK];
-    const uint64_t base = (uint64_t)blockIdx.x * KD_SCAN_TILE;
-    uint64_t v = 0;
-    for (uint32_t j = 0; j < KD_SCAN_TILE / KD_BLOCK; j++) {
-        const uint64_t i = base + j * KD_BLOCK + threadIdx.x;
-        if (i < n) v += head[i].count;
-    }
-    uint64_t total;
-    (void)kd_block_scan(v, sh, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(KD_BLOCK) void kids_scan_bases_kernel(uint64_t *sums, uint64_t tiles)
-{
-    __shared__ uint64_t sh[KD_BLOCK];
-    uint64_t carry = 0;
-    for (uint64_t q = 0; q < tiles; q += KD_BLOCK) {
-        const uint64_t i = q + threadIdx.x;
-        const uint64_t v = i < tiles ? sums[i] : 0;
-        uint64_t total;
-        const uint64_t ex = kd_block_scan(v, sh, total);
-        if (i < tiles) sums[i] = carry + ex;
-        carry += total;
-    }
-}
-
-/* sums = the tiles' bases, or null for a batch of one tile */
-__global__ __launch_bounds__(KD_BLOCK) void kids_scan_tile_kernel(const dg_kids_head *head, uint64_t n, const uint64_t *sums,
-                                                                  uint64_t *rec_off)
-{
-    __shared__ uint64_t sh[KD_BLOCK];
-    constexpr uint32_t PER = KD_SCAN_TILE / KD_BLOCK;
-    const uint64_t first = (uint64_t)blockIdx.x * KD_SCAN_TILE + (uint64_t)threadIdx.x * PER;
-    uint32_t c[PER];
-    uint64_t v = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < PER; j++) {
-        c[j] = first + j < n ? head[first + j].count : 0u;
-        v += c[j];
-    }
-    uint64_t total;
-    uint64_t off = kd_block_scan(v, sh, total) + (sums ? sums[blockIdx.x] : 0ull);
-#pragma unroll
-    for (uint32_t j = 0; j < PER; j++) {
-        if (first + j >= n) continue;
-        rec_off[first + j] = off;
-        off += c[j];
-        if (first + j == n - 1) rec_off[n] = off;
-    }
-}
-
 void launch_kids_count(hipStream_t s, const KDParams &A)
 {
     hipLaunchKernelGGL(kids_kernel<0>, dim3((uint32_t)((A.n + KD_BLOCK - 1) / KD_BLOCK)), dim3(KD_BLOCK), 0, s, A);
     hipLaunchKernelGGL(kids_deep_kernel<0>, dim3(KD_DEEP_BLOCKS), dim3(KD_DEEP_BLOCK), 0, s, A);
 }
 
+/* rec_off[i] = the sum of head[0..i).count as 64-bit, rec_off[n] the total */
 void launch_kids_scan(hipStream_t s, const KDParams &A, uint64_t *sums)
 {
-    const uint32_t tiles = (uint32_t)((A.n + KD_SCAN_TILE - 1) / KD_SCAN_TILE);
-    if (tiles > 1) {
-        hipLaunchKernelGGL(kids_scan_sums_kernel, dim3(tiles), dim3(KD_BLOCK), 0, s, A.head, A.n, sums);
-        hipLaunchKernelGGL(kids_scan_bases_kernel, dim3(1), dim3(KD_BLOCK), 0, s, sums, (uint64_t)tiles);
-    }
-    hipLaunchKernelGGL(kids_scan_tile_kernel, dim3(tiles), dim3(KD_BLOCK), 0, s, A.head, A.n, tiles > 1 ? sums : nullptr,
-                       A.rec_off);
+    launch_scan(s, ScanKidsHead{A.head}, A.n, sums, A.rec_off);
 }
 
 void launch_kids_emit(hipStream_t s, const KDParams &A, uint32_t wide_blocks)

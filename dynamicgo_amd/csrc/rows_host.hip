@@ -6,19 +6,14 @@
  */
 #include <string.h>
 
-#include "host_internal.h"
+#include "plan_internal.h"
 #include "rows_device.h"
 
 using namespace dg;
 
 static const uint64_t ROWS_WS = (uint64_t)TG_DEEP_DEPTH * TG_DEEP_LANES * 8;
 
-static bool kind_is_list(uint32_t kind) { return (kind & DG_COL_LIST) != 0; }
-static bool kind_ok(uint32_t kind)
-{
-    return (kind >= DG_COL_BOOL && kind <= DG_COL_LEN) || kind == (DG_COL_LIST | DG_COL_INT) ||
-           kind == (DG_COL_LIST | DG_COL_F64);
-}
+static const PlanKinds ROWS_KINDS{col_kind_ok, "rows", "sub-paths", "kind"};
 
 /* one batch (device pointers) */
 struct RowsBatch {
@@ -37,10 +32,8 @@ struct RowsBatch {
 /* one batch on stream s (ctx mutex held): head pass -> scan -> index pass ->
  * cell pass, each lane pass followed by its deep pass. counted: head and
  * row_off come from an earlier launch with the same batch (the host entry's
- * second launch). The queue, the two counters (alternating per pass; a deep
- * pass zeroes the other), the counts, the tile sums, the scratch index and the
- * deep frames are one per context: a launch on another stream than the
- * previous one waits for it. */
+ * second launch). All on the component's pass state (the counters alternate
+ * per pass), which also orders the counts and the scratch index. */
 static int rows_launch(dg_ctx *c, const dg_rows *rp, uint8_t root_type, const RowsBatch &b, bool counted, hipStream_t s)
 {
     const uint64_t n = b.n, P = rp->sub_hdr.n_paths;
@@ -58,55 +51,47 @@ static int rows_launch(dg_ctx *c, const dg_rows *rp, uint8_t root_type, const Ro
     if (!b.val != !b.cell) return set_err(DG_E_INVALID, "values without cells, or cells without values");
     const bool cells = b.val && b.row_cap;
     const bool indexed = cells || (b.index && b.row_cap); /* an index without cells: the caller's own row walk */
-    bool wants_len = false;
-    uint64_t kinds = 0;
-    for (uint32_t k = 0; k < P; k++) {
-        wants_len |= rp->kinds[k] == DG_COL_STR || kind_is_list(rp->kinds[k]);
-        kinds |= (uint64_t)rp->kinds[k] << (k * 8);
-    }
-    if (cells && wants_len && !b.len) return set_err(DG_E_INVALID, "a STR or list column needs d_len");
+    if (cells && wants_len(rp->kinds, P) && !b.len) return set_err(DG_E_INVALID, "a STR or list column needs d_len");
     if (indexed && (b.row_cap > 0xFFFFFFFFull || b.row_cap * P > 0xFFFFFFFFull))
         return set_err(DG_E_INVALID, "%llu rows x %llu columns: 2^32 pairs or more", (unsigned long long)b.row_cap,
                        (unsigned long long)P);
+    PassState &st = c->rows;
     int rc;
-    if (!c->rows.ws && ((rc = c->rows.ws.alloc(ROWS_WS)) || (rc = c->rows_cnt.init(c->rows_cnt_buf, 1)))) return rc;
     /* the previous launch may still use the old queue, counts, sums and index */
-    if ((rc = c->rows.grow(c->rows_list, std::max(n, cells ? b.row_cap * P : 0))) || (rc = c->rows.grow(c->rows_counts, n)) ||
-        (rc = c->rows.grow(c->rows_sums, (n + CL_SCAN_TILE - 1) / CL_SCAN_TILE)) ||
-        (cells && !b.index && (rc = c->rows.grow(c->rows_index, b.row_cap))))
+    if ((rc = st.first_use(ROWS_WS, 1)) ||
+        (rc = st.room(std::max(n, cells ? b.row_cap * P : 0), (n + SCAN_TILE - 1) / SCAN_TILE)) ||
+        (rc = st.grow(c->rows_counts, n)) || (cells && !b.index && (rc = st.grow(c->rows_index, b.row_cap))))
         return rc;
-    HIPCHK(c->rows.acquire(s));
     RWParams A;
     memset(&A, 0, sizeof A);
     A.par.src = b.src, A.par.in_off = b.in_off, A.par.root_type = root_type;
     A.par.blob = rp->d_blob, A.par.off_steps = rp->hdr.off_steps, A.par.off_pool = rp->hdr.off_pool;
     A.sub.blob = rp->d_sub, A.sub.off_steps = rp->sub_hdr.off_steps, A.sub.off_pool = rp->sub_hdr.off_pool;
     A.sub.P = (uint32_t)P;
-    A.n = n, A.n_steps = rp->hdr.n_steps, A.kinds = kinds; /* one parent path: all the steps are its own */
+    A.n = n, A.n_steps = rp->hdr.n_steps, A.kinds = pack_kinds(rp->kinds, P); /* one parent path: all the steps are its own */
     A.head = b.head, A.count = c->rows_counts, A.row_off = b.row_off;
     A.idx = b.index ? b.index : (dg_row_ent *)c->rows_index, A.row_cap = b.row_cap;
     A.val = b.val, A.cell = (uint64_t *)(void *)b.cell, A.len = b.len;
-    A.deep_list = c->rows_list, A.ws = (uint64_t *)(void *)c->rows.ws;
-    hipError_t e = hipSuccess;
-    /* one lane pass with its deep pass on the counter set whose turn it is */
-    auto pass = [&](void (*launch)(hipStream_t, const RWParams &)) {
-        A.cnt = c->rows_cnt.mine(), A.reset = c->rows_cnt.other();
-        launch(s, A);
-        e = hipGetLastError();
-        c->rows_cnt.finish(e == hipSuccess, s);
-    };
-    if (!counted) {
-        pass(launch_rows_head);
-        if (e == hipSuccess) {
-            launch_cols_scan(s, c->rows_counts, n, c->rows_sums, b.row_off);
-            e = hipGetLastError();
+    A.deep_list = st.list, A.ws = (uint64_t *)(void *)st.ws;
+    return st.enqueue(s, "rows", [&] {
+        const auto pass = [&](void (*launch)(hipStream_t, const RWParams &)) {
+            return st.pass(s, [&](uint32_t *mine, uint32_t *other) {
+                A.cnt = mine, A.reset = other;
+                launch(s, A);
+            });
+        };
+        hipError_t e = hipSuccess;
+        if (!counted) {
+            e = pass(launch_rows_head);
+            if (e == hipSuccess) {
+                launch_cols_scan(s, c->rows_counts, n, st.sums, b.row_off);
+                e = hipGetLastError();
+            }
         }
-    }
-    if (e == hipSuccess && indexed) pass(launch_rows_index);
-    if (e == hipSuccess && cells) pass(launch_rows_cells);
-    HIPCHK(c->rows.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "rows launch: %s", hipGetErrorString(e));
-    return DG_OK;
+        if (e == hipSuccess && indexed) e = pass(launch_rows_index);
+        if (e == hipSuccess && cells) e = pass(launch_rows_cells);
+        return e;
+    });
 }
 
 static int rows_args(const dg_ctx *c, const dg_rows *rp)
@@ -125,33 +110,18 @@ int dg_rows_create(dg_ctx *c, const void *parent_blob, size_t parent_len, const 
     int rc;
     if ((rc = dg_i_path_validate(parent_blob, parent_len, h)) || (rc = dg_i_path_validate(sub_blob, sub_len, sh))) return rc;
     if (h.n_paths != 1) return set_err(DG_E_ARG, "rows: %u parent paths (exactly 1)", h.n_paths);
-    if (n_kinds != sh.n_paths || n_kinds > DG_ROWS_MAX_COLS) return set_err(DG_E_ARG, "%u kinds for %u sub-paths", n_kinds, sh.n_paths);
-    for (uint32_t k = 0; k < n_kinds; k++)
-        if (!kind_ok(kinds[k])) return set_err(DG_E_ARG, "column %u: unknown kind %u", k, kinds[k]);
+    if ((rc = plan_kinds_check(sh, kinds, n_kinds, ROWS_KINDS))) return rc;
     Entry g(c, true);
     if (g.rc) return g.rc;
-    std::unique_ptr<dg_rows> rp(new dg_rows());
-    rp->ctx = c;
-    rp->hdr = h, rp->sub_hdr = sh;
-    memset(rp->kinds, 0, sizeof rp->kinds);
-    memcpy(rp->kinds, kinds, n_kinds);
-    if ((rc = upload_blob(rp->d_blob, parent_blob, h.total_len, "rows")) ||
-        (rc = upload_blob(rp->d_sub, sub_blob, sh.total_len, "rows")))
-        return rc;
+    std::unique_ptr<dg_rows> rp;
+    if ((rc = plan_new(c, h, parent_blob, kinds, n_kinds, "rows", rp))) return rc;
+    rp->sub_hdr = sh;
+    if ((rc = upload_blob(rp->d_sub, sub_blob, sh.total_len, "rows"))) return rc;
     *out = rp.release();
     return DG_OK;
 }
 
-void dg_rows_destroy(dg_rows *p)
-{
-    if (!p) return;
-    {
-        Entry g(p->ctx, true); /* the blobs go under the context lock, on its device */
-        p->d_blob.reset();
-        p->d_sub.reset();
-    }
-    delete p;
-}
+void dg_rows_destroy(dg_rows *p) { destroy_with_blob(p); }
 
 uint32_t dg_rows_count(const dg_rows *p) { return p ? p->sub_hdr.n_paths : 0; }
 
@@ -174,30 +144,9 @@ int dg_rows_list_device(dg_ctx *c, const dg_rows *rp, uint32_t k, const uint8_t 
     if (int rc = rows_args(c, rp)) return rc;
     Entry g(c, true, stream);
     if (g.rc) return g.rc;
-    const hipStream_t s = g.s;
-    const uint64_t n = n_rows;
     if (k >= rp->sub_hdr.n_paths || !kind_is_list(rp->kinds[k])) return set_err(DG_E_ARG, "column %u is no list column", k);
-    if (!d_elem_off) return set_err(DG_E_INVALID, "null buffer");
-    if (((uintptr_t)d_elem_off & 7) || ((uintptr_t)d_elems & 7))
-        return set_err(DG_E_INVALID, "offsets or elements not 8-byte aligned");
-    if (n > 0xFFFFFFFFull) return set_err(DG_E_INVALID, "%llu rows", (unsigned long long)n);
-    if (n == 0) {
-        HIPCHK(hipMemsetAsync(d_elem_off, 0, 8, s));
-        return DG_OK;
-    }
-    if (!d_thrift || !d_val_k || !d_cell_k || !d_len_k) return set_err(DG_E_INVALID, "null buffer");
-    if (int rc = c->rows.grow(c->rows_sums, (n + CL_SCAN_TILE - 1) / CL_SCAN_TILE)) return rc;
-    HIPCHK(c->rows.acquire(s));
-    launch_cols_scan(s, d_len_k, n, c->rows_sums, d_elem_off);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && d_elems && elem_cap) {
-        const CLEmit E{d_thrift, n, d_val_k, (const uint64_t *)(const void *)d_cell_k, d_elem_off, d_elems, elem_cap};
-        launch_cols_emit(s, E, (uint32_t)std::max(c->n_cu, 1) * 8u, false);
-        e = hipGetLastError();
-    }
-    HIPCHK(c->rows.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "rows list launch: %s", hipGetErrorString(e));
-    return DG_OK;
+    return dg_i_list_launch(c, c->rows, false, true,
+                            ListCol{d_thrift, n_rows, d_val_k, d_cell_k, d_len_k, d_elem_off, d_elems, elem_cap}, g.s);
 }
 
 int dg_rows_batch_host(dg_ctx *c, const dg_rows *rp, uint8_t root_type, const uint8_t *thrift, const uint64_t *in_off,

@@ -28,10 +28,7 @@ static uint32_t tget_spread(const dg_ctx *c, uint64_t max_len)
     return 1;
 }
 
-/* one batch on stream s (ctx mutex held). The deep queue, its two counters
- * and the deep frames are one per context: a launch on another stream than
- * the previous one waits for it. Launches alternate between the counters and
- * each deep pass zeroes the other one (no memset per launch). */
+/* one batch on stream s (ctx mutex held), on the component's pass state */
 int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const TGetBatch &b, hipStream_t s)
 {
     const uint64_t n = b.n;
@@ -41,10 +38,9 @@ int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const TGetBatch
     const uint64_t pairs = n * ps->hdr.n_paths;
     if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
         return set_err(DG_E_INVALID, "batch of %llu messages x %u paths", (unsigned long long)n, ps->hdr.n_paths);
+    PassState &st = c->tget;
     int rc;
-    if (!c->tget.ws && ((rc = c->tget.ws.alloc(TGET_WS)) || (rc = c->tget_cnt.init(c->tget_cnt_buf, 1)))) return rc;
-    if ((rc = c->tget.grow(c->tget_list, pairs))) return rc; /* the previous launch may still fill the old list */
-    HIPCHK(c->tget.acquire(s));
+    if ((rc = st.first_use(TGET_WS, 1)) || (rc = st.room(pairs))) return rc;
     TGParams A;
     memset(&A, 0, sizeof A);
     A.src = b.src;
@@ -58,20 +54,15 @@ int tget_launch(dg_ctx *c, const dg_path *ps, uint8_t root_type, const TGetBatch
     A.rec = b.rec;
     A.val_off = b.val_off;
     A.val_len = b.val_len;
-    A.deep_list = c->tget_list;
-    A.deep_count = c->tget_cnt.mine();
-    A.reset_count = c->tget_cnt.other();
-    A.ws = (uint64_t *)(void *)c->tget.ws;
-    launch_tget_pass(s, A, tget_spread(c, b.max_len));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        launch_tget_deep(s, A);
-        e = hipGetLastError();
-    }
-    c->tget_cnt.finish(e == hipSuccess, s);
-    HIPCHK(c->tget.publish(s));
-    if (e != hipSuccess) return set_err(DG_E_HIP, "tget launch: %s", hipGetErrorString(e));
-    return DG_OK;
+    A.deep_list = st.list;
+    A.ws = (uint64_t *)(void *)st.ws;
+    return st.enqueue(s, "tget", [&] {
+        return st.pass(s, [&](uint32_t *mine, uint32_t *other) {
+            A.deep_count = mine, A.reset_count = other;
+            launch_tget_pass(s, A, tget_spread(c, b.max_len));
+            if (hipPeekAtLastError() == hipSuccess) launch_tget_deep(s, A);
+        });
+    });
 }
 
 int dg_i_path_validate(const void *blob, size_t len, dg_path_hdr &h)

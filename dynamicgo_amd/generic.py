@@ -182,6 +182,23 @@ class _Handle:
         self.close()
 
 
+class _KindPlan(_Handle):
+    """What ColumnPlan and EntryPlan share: the constructor of a plan of
+    (path, kind) columns. A class names the library's create and count entries
+    (_create, _count) and the function that resolves a kind (_kind)."""
+    _create = _count = _kind = None
+
+    def __init__(self, columns, desc=None, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.kinds = [self._kind(k) for _, k in columns]
+        self.blob = compile_paths([p for p, _ in columns], desc)
+        h = C.c_void_p()
+        _lib.check(getattr(_lib.lib(), self._create)(self.ctx.h, self.blob, len(self.blob), bytes(self.kinds),
+                                                     len(self.kinds), C.byref(h)))
+        self.h = h
+        self.count = int(getattr(_lib.lib(), self._count)(h))
+
+
 @contextlib.contextmanager
 def _unless_given(made, given):
     """Closes `made` after the block unless it is the caller's own `given`."""
@@ -1004,21 +1021,14 @@ def col_kind(kind) -> int:
     return int(k)
 
 
-class ColumnPlan(_Handle):
+class ColumnPlan(_KindPlan):
     """1 to 8 columns, each a path (a list of Path steps; PathFieldName is
     resolved through `desc`) and a kind (col_kind), on one context's device
     (dg_cols). `columns` is a list of (path, kind)."""
-    _destroy = "dg_cols_destroy"
+    _destroy, _create, _count, _kind = "dg_cols_destroy", "dg_cols_create", "dg_cols_count", staticmethod(col_kind)
 
     def __init__(self, columns, desc=None, ctx: Optional[Context] = None):
-        self.ctx = ctx or default_context()
-        self.kinds = [col_kind(k) for _, k in columns]
-        self.blob = compile_paths([p for p, _ in columns], desc)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().dg_cols_create(self.ctx.h, self.blob, len(self.blob), bytes(self.kinds), len(self.kinds),
-                                             C.byref(h)))
-        self.h = h
-        self.count = int(_lib.lib().dg_cols_count(h))
+        super().__init__(columns, desc, ctx)
         self.lists = [k for k, kind in enumerate(self.kinds) if kind & COL_LIST]
 
 
@@ -1324,21 +1334,11 @@ def ent_kind(kind) -> int:
     return int(k)
 
 
-class EntryPlan(_Handle):
+class EntryPlan(_KindPlan):
     """1 to 8 entry columns, each a path (a list of Path steps; PathFieldName
     is resolved through `desc`) and a kind (ent_kind), on one context's device
     (dg_ents). `columns` is a list of (path, kind)."""
-    _destroy = "dg_ents_destroy"
-
-    def __init__(self, columns, desc=None, ctx: Optional[Context] = None):
-        self.ctx = ctx or default_context()
-        self.kinds = [ent_kind(k) for _, k in columns]
-        self.blob = compile_paths([p for p, _ in columns], desc)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().dg_ents_create(self.ctx.h, self.blob, len(self.blob), bytes(self.kinds), len(self.kinds),
-                                             C.byref(h)))
-        self.h = h
-        self.count = int(_lib.lib().dg_ents_count(h))
+    _destroy, _create, _count, _kind = "dg_ents_destroy", "dg_ents_create", "dg_ents_count", staticmethod(ent_kind)
 
 
 def entries_device(plan: EntryPlan, thrift, in_off, n: int, val, cell, lens, spans, root_type: int = STRUCT,
