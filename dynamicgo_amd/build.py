@@ -32,7 +32,8 @@ UNITS = ("j2t_kern_wave.hip", "j2t_kern_wave5.hip", "j2t_kern_small.hip", "j2t_k
 HEADERS = ("j2t_small.h", "j2t_wave.h", "j2t_machine.h", "j2t_device.h", "j2t_fast.h", "dg_tables.h", "host_internal.h",
            "t2j_device.h", "t2j_tables.h", "j2t_flat.h", "t2j_wave.h", "tget_device.h", "cut_device.h", "edit_device.h",
            "kids_device.h", "editm_device.h", "flat_image.h", "host_layout.h", "cols_device.h", "ents_device.h",
-           "vals_device.h", "evals_device.h", "fl_classify.h", "rows_device.h", "walk_kern.h", "scan_kern.h", "scan_defs.h", "plan_internal.h")
+           "vals_device.h", "evals_device.h", "fl_classify.h", "rows_device.h", "walk_kern.h", "scan_kern.h", "scan_defs.h", "plan_internal.h",
+           "write_internal.h")
 
 
 def source_hash(extra_flags=()) -> str:

@@ -122,26 +122,15 @@ TGI EVCell ev_cell(uint32_t kind, uint32_t fh, uint32_t stop, bool present, uint
     return z;
 }
 
-/* cell q decoded from the inputs */
-struct EVPair {
-    uint32_t i, j, kind, fh, stop;
-    int32_t id;
-};
-TGI EVPair ev_pair(const EVParams &A, uint64_t q)
-{
-    EVPair p;
-    p.i = (uint32_t)q / A.K, p.j = (uint32_t)q - p.i * A.K;
-    p.kind = A.kinds[p.j], p.id = A.ids[p.j];
-    p.fh = A.has_ids ? 3u : 0u, p.stop = A.has_ids && p.j == A.K - 1;
-    return p;
-}
+/* cell q decoded from the inputs (vl_cell, vals_device.h), and its item */
+using EVPair = VLCell;
+TGI EVPair ev_pair(const EVParams &A, uint64_t q) { return vl_cell(A, q); }
 TGI EVCell ev_pair_cell(const EVParams &A, const EVPair &p)
 {
     const dg_eval_col &c = A.col[p.j];
-    const bool present = !(A.has_ids && c.d_present) || c.d_present[p.i] != 0;
     uint64_t a = 0, b = 0;
-    if (present) a = c.d_ent_off[p.i], b = c.d_ent_off[p.i + 1];
-    return ev_cell(p.kind, p.fh, p.stop, present, a, b, c.n_ent, A.pos[p.j]);
+    if (p.present) a = c.d_ent_off[p.i], b = c.d_ent_off[p.i + 1];
+    return ev_cell(p.kind, p.fh, p.stop, p.present, a, b, c.n_ent, A.pos[p.j]);
 }
 
 /* what precedes the entries of the item of `len` bytes and `cnt` entries at
@@ -152,15 +141,12 @@ TGI void ev_head(uint32_t kind, int32_t id, uint32_t fh, uint32_t stop, uint32_t
 {
     VLBytes h{0, 0, 0};
     if (len > stop) {
-        if (fh) vl_push(h, (uint64_t)ev_wire(kind) | (uint64_t)__builtin_bswap16((uint16_t)id) << 8, 3);
+        vl_field(h, fh, ev_wire(kind), id);
         if (ev_is_map(kind))
             vl_push(h, (uint64_t)ev_kt(kind) | (uint64_t)ev_vt(kind) << 8 | (uint64_t)__builtin_bswap32(cnt) << 16, 6);
         else vl_push(h, (uint64_t)TT_STRING | (uint64_t)__builtin_bswap32(cnt) << 8, 5);
     }
-    const bool far_stop = stop && len != h.n + 1; /* entries lie between */
-    if (stop && !far_stop) vl_push(h, 0, 1);
-    (void)vl_flush(h, out, pos, cap);
-    if (far_stop && pos + len - 1 < cap) out[pos + len - 1] = 0;
+    vl_close(h, stop, len, out, pos, cap);
 }
 
 /* a payload of len bytes at out + at in 8-byte units, one unaligned 8-byte load each (vl_unit: up to 7 bytes past it) */

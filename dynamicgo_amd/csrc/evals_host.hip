@@ -10,8 +10,8 @@
 
 /* the size and kind helpers of evals_device.h serve the host here too */
 #define TGI __host__ __device__ __forceinline__
-#include "host_internal.h"
 #include "evals_device.h"
+#include "write_internal.h"
 
 using namespace dg;
 
@@ -46,36 +46,31 @@ static EVWork ev_work(const dg_evals *ep, uint64_t n, const uint64_t *n_ent)
     return w;
 }
 
+/* a buffer the column's kind reads is null; the arenas may be: a column whose strings are all empty reads neither */
+static bool ev_col_null(const dg_eval_col &v, uint32_t kt, uint32_t vt)
+{
+    return !v.d_ent_off || (v.n_ent && (!v.d_val || (kt && !v.d_key) || (kt == TT_STRING && !v.d_key_len) ||
+                                        (vt == TT_STRING && !v.d_val_len)));
+}
+
 /* One batch on stream s (ctx mutex held). Everything proportional to the
  * cells or the entries lies in the caller's d_work. */
-static int evals_launch(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols, uint64_t n, uint64_t out_base, uint8_t *d_out,
-                        uint64_t cap, uint64_t *d_out_off, uint8_t *d_status, void *d_work, uint64_t work_bytes, hipStream_t s)
+static int evals_launch(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols, const WriteCall &call, void *d_work,
+                        uint64_t work_bytes, hipStream_t s)
 {
     const uint32_t K = ep->K;
-    if (!cols) return set_err(DG_E_INVALID, "null columns");
+    const uint64_t n = call.n;
+    if (int rc = write_prologue(ep, cols, call); rc || !n) return rc;
     uint64_t n_ent[DG_VALS_MAX_COLS], ents = 0;
     for (uint32_t k = 0; k < K; k++) {
         const dg_eval_col &v = cols[k];
         const uint32_t kt = ev_kt(ep->kinds[k]), vt = ev_vt(ep->kinds[k]);
-        if (v.d_present && !ep->ids) return set_err(DG_E_ARG, "column %u: d_present in a plan without field ids", k);
-        if (v.n_ent > DG_EVALS_MAX_ENT)
-            return set_err(DG_E_ARG, "column %u: %llu entries (at most %llu)", k, (unsigned long long)v.n_ent,
-                           (unsigned long long)DG_EVALS_MAX_ENT);
         n_ent[k] = v.n_ent, ents += v.n_ent;
-        if (n == 0) continue;
-        /* the arenas may be null: a column whose strings are all empty reads neither */
-        if (!v.d_ent_off || (v.n_ent && (!v.d_val || (kt && !v.d_key) || (kt == TT_STRING && !v.d_key_len) ||
-                                          (vt == TT_STRING && !v.d_val_len))))
-            return set_err(DG_E_INVALID, "column %u: null buffer", k);
+        if (ev_col_null(v, kt, vt)) return set_err(DG_E_INVALID, "column %u: null buffer", k);
         if (((uintptr_t)v.d_ent_off & 7) || ((uintptr_t)v.d_key & 7) || ((uintptr_t)v.d_val & 7) || ((uintptr_t)v.d_key_len & 3) ||
             ((uintptr_t)v.d_val_len & 3))
             return set_err(DG_E_INVALID, "column %u: offsets, keys, values or lengths not aligned", k);
     }
-    if (n == 0) return DG_OK;
-    if (!d_out_off || ((uintptr_t)d_out_off & 7)) return set_err(DG_E_INVALID, "d_out_off null or not 8-byte aligned");
-    const uint64_t pairs = n * K;
-    if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
-        return set_err(DG_E_INVALID, "batch of %llu messages x %u columns", (unsigned long long)n, K);
     const EVWork w = ev_work(ep, n, n_ent);
     if (!d_work || ((uintptr_t)d_work & 7)) return set_err(DG_E_INVALID, "d_work null or not 8-byte aligned");
     if (work_bytes < w.bytes)
@@ -83,13 +78,9 @@ static int evals_launch(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols, 
     uint8_t *const wk = (uint8_t *)d_work;
     uint64_t *const sums = (uint64_t *)(wk + w.sums);
     EVParams A;
-    memset(&A, 0, sizeof A);
-    memcpy(A.col, cols, K * sizeof *cols);
-    memcpy(A.kinds, ep->kinds, sizeof A.kinds);
-    memcpy(A.ids, ep->field_ids, sizeof A.ids);
-    A.K = K, A.has_ids = ep->ids, A.pairs = pairs, A.base = out_base, A.cap = cap;
+    write_params(A, ep, cols, call);
+    const uint64_t pairs = A.pairs;
     A.len = (uint32_t *)(wk + w.len), A.cnt = (uint32_t *)(wk + w.cnt), A.cnt_off = (uint64_t *)(wk + w.cnt_off);
-    A.off = d_out_off, A.status = d_status, A.out = d_out;
     hipError_t e = hipSuccess;
     for (uint32_t k = 0; k < K && e == hipSuccess; k++) {
         if (w.pos[k] == ~0ull) continue;
@@ -106,17 +97,14 @@ static int evals_launch(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols, 
         e = hipGetLastError();
     }
     if (e == hipSuccess) {
-        launch_cols_scan(s, A.len, pairs, sums, d_out_off);
+        launch_cols_scan(s, A.len, pairs, sums, call.d_out_off);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && out_base) {
-        VLParams R;
-        memset(&R, 0, sizeof R);
-        R.off = d_out_off, R.pairs = pairs, R.base = out_base;
-        launch_vals_rebase(s, R);
+    if (e == hipSuccess && call.out_base) {
+        launch_vals_rebase(s, call.d_out_off, pairs + 1, call.out_base);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && d_out && cap > out_base) {
+    if (e == hipSuccess && call.d_out && call.cap > call.out_base) {
         launch_cols_scan(s, A.cnt, pairs, sums, A.cnt_off);
         e = hipGetLastError();
         if (e == hipSuccess) {
@@ -130,39 +118,11 @@ static int evals_launch(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols, 
     return DG_OK;
 }
 
-/* The payloads of one side (keys or values) of a host column on the device:
- * from the first to the last byte an entry of an OK cell reads; the offsets of
- * those entries are rebased to what was uploaded, every other one is 0. */
-static int payloads_to_device(const uint64_t *off, const uint32_t *len, const uint8_t *src, const std::vector<uint8_t> &owned,
-                              DevArr<uint64_t> &d_off, DevArr<uint8_t> &d_src)
-{
-    const uint64_t n_ent = owned.size();
-    uint64_t lo = ~0ull, hi = 0;
-    for (uint64_t e = 0; e < n_ent; e++)
-        if (owned[e] && len[e]) lo = std::min(lo, off[e]), hi = std::max(hi, off[e] + len[e]);
-    if (hi <= lo) lo = hi = 0;
-    std::vector<uint64_t> tmp(n_ent);
-    for (uint64_t e = 0; e < n_ent; e++) tmp[e] = owned[e] && len[e] ? off[e] - lo : 0;
-    if (int rc = to_device(d_off, tmp.data(), n_ent)) return rc;
-    return to_device(d_src, src + lo, hi - lo, 16);
-}
-
 extern "C" {
 
 int dg_evals_create(dg_ctx *c, const uint16_t *kinds, uint32_t K, const int16_t *field_ids, dg_evals **out)
 {
-    if (!c || !kinds || !out) return set_err(DG_E_INVALID, "null ctx/kinds/out");
-    if (K < 1 || K > DG_VALS_MAX_COLS) return set_err(DG_E_ARG, "%u columns (1 to %u)", K, DG_VALS_MAX_COLS);
-    std::unique_ptr<dg_evals> ep(new dg_evals());
-    memset(ep.get(), 0, sizeof(dg_evals));
-    ep->ctx = c, ep->K = K, ep->ids = field_ids != nullptr;
-    for (uint32_t k = 0; k < K; k++) {
-        if (!ev_kind_ok(kinds[k])) return set_err(DG_E_ARG, "column %u: unknown kind %u", k, kinds[k]);
-        ep->kinds[k] = kinds[k];
-        if (field_ids) ep->field_ids[k] = field_ids[k];
-    }
-    *out = ep.release();
-    return DG_OK;
+    return write_plan_create(c, kinds, K, field_ids, [](uint32_t kind) { return ev_kind_ok(kind); }, out);
 }
 
 void dg_evals_destroy(dg_evals *p) { delete p; }
@@ -184,27 +144,17 @@ int dg_evals_batch_device(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols
 {
     Entry g(c, c && ep && ep->ctx == c, stream, "null ctx/plan, or a plan of another context");
     if (g.rc) return g.rc;
-    return evals_launch(c, ep, cols, n, out_base, d_out, cap, d_out_off, d_status, d_work, work_bytes, g.s);
+    return evals_launch(c, ep, cols, WriteCall{n, out_base, d_out, cap, d_out_off, d_status}, d_work, work_bytes, g.s);
 }
 
 int dg_evals_batch_host(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols, uint64_t n, uint8_t *out, uint64_t cap,
                         uint64_t *out_off, uint8_t *status, uint64_t *need)
 {
-    if (!c || !ep || ep->ctx != c || !cols) return set_err(DG_E_INVALID, "null ctx/plan/columns, or a plan of another context");
+    int rc = write_host_prologue(c, ep, cols, n, out_off, need);
+    if (rc || !n) return rc;
     const uint32_t K = ep->K;
     uint64_t n_ent[DG_VALS_MAX_COLS];
-    for (uint32_t k = 0; k < K; k++) {
-        if (cols[k].d_present && !ep->ids) return set_err(DG_E_ARG, "column %u: d_present in a plan without field ids", k);
-        if (cols[k].n_ent > DG_EVALS_MAX_ENT)
-            return set_err(DG_E_ARG, "column %u: %llu entries (at most %llu)", k, (unsigned long long)cols[k].n_ent,
-                           (unsigned long long)DG_EVALS_MAX_ENT);
-        n_ent[k] = cols[k].n_ent;
-    }
-    if (n == 0) return empty_batch(out_off, need);
-    if (!out_off) return set_err(DG_E_INVALID, "null buffer");
-    const uint64_t pairs = n * K;
-    if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
-        return set_err(DG_E_INVALID, "batch of %llu messages x %u columns", (unsigned long long)n, K);
+    for (uint32_t k = 0; k < K; k++) n_ent[k] = cols[k].n_ent;
     Entry g(c, true);
     if (g.rc) return g.rc;
     /* the inputs on the device: offsets and per-entry arrays whole, the
@@ -217,16 +167,13 @@ int dg_evals_batch_host(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols, 
     };
     std::vector<ColDev> dev(K);
     std::vector<dg_eval_col> dc(K);
-    int rc;
     for (uint32_t k = 0; k < K; k++) {
         const dg_eval_col &h = cols[k];
         const uint32_t kind = ep->kinds[k], kt = ev_kt(kind), vt = ev_vt(kind);
         const uint64_t ne = h.n_ent;
         memset(&dc[k], 0, sizeof dc[k]);
         dc[k].n_ent = ne;
-        if (!h.d_ent_off || (ne && (!h.d_val || (kt && !h.d_key) || (kt == TT_STRING && !h.d_key_len) ||
-                                    (vt == TT_STRING && !h.d_val_len))))
-            return set_err(DG_E_INVALID, "column %u: null buffer", k);
+        if (ev_col_null(h, kt, vt)) return set_err(DG_E_INVALID, "column %u: null buffer", k);
         if (h.d_present) {
             if ((rc = to_device(dev[k].present, h.d_present, n))) return rc;
             dc[k].d_present = dev[k].present;
@@ -256,34 +203,24 @@ int dg_evals_batch_host(dg_ctx *c, const dg_evals *ep, const dg_eval_col *cols, 
             if (ev_cell(kind, ep->ids ? 3u : 0u, ep->ids && k == K - 1, true, a, b, ne, pos.data()).cnt)
                 std::fill(owned.begin() + a, owned.begin() + b, 1);
         }
+        const auto live = [&owned](uint64_t e) { return owned[e] != 0; }; /* an OK cell owns the entry */
         if (kt == TT_STRING) {
-            if ((rc = payloads_to_device(h.d_key, h.d_key_len, h.d_key_src, owned, dev[k].key, dev[k].key_src))) return rc;
+            if ((rc = payloads_to_device(h.d_key, h.d_key_len, h.d_key_src, ne, live, dev[k].key, dev[k].key_src))) return rc;
             dc[k].d_key = dev[k].key, dc[k].d_key_src = dev[k].key_src;
         }
         if (vt == TT_STRING) {
-            if ((rc = payloads_to_device(h.d_val, h.d_val_len, h.d_val_src, owned, dev[k].val, dev[k].val_src))) return rc;
+            if ((rc = payloads_to_device(h.d_val, h.d_val_len, h.d_val_src, ne, live, dev[k].val, dev[k].val_src))) return rc;
             dc[k].d_val = dev[k].val, dc[k].d_val_src = dev[k].val_src;
         }
     }
-    DevArr<uint64_t> d_off;
-    DevArr<uint8_t> d_status, d_out, d_work;
+    DevArr<uint8_t> d_work;
     const uint64_t work = ev_work(ep, n, n_ent).bytes;
-    if ((rc = d_off.alloc(pairs + 1)) || (rc = d_status.alloc(pairs)) || (rc = d_work.alloc(work + 8))) return rc;
+    if ((rc = d_work.alloc(work + 8))) return rc;
     const hipStream_t s = g.s;
-    if ((rc = evals_launch(c, ep, dc.data(), n, 0, nullptr, 0, d_off, d_status, d_work, work, s))) return rc; /* sizing */
-    HIPCHK(hipMemcpyAsync(out_off, d_off.p, (pairs + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (status) HIPCHK(hipMemcpyAsync(status, d_status.p, pairs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const uint64_t want = out_off[pairs];
-    if (need) *need = want;
-    if (!out && !cap) return DG_OK; /* sizing */
-    if (want > cap || (!out && want)) return set_err(DG_E_NOMEM, "values need %llu bytes", (unsigned long long)want);
-    if (!want) return DG_OK;
-    if ((rc = d_out.alloc(want + 16)) || (rc = evals_launch(c, ep, dc.data(), n, 0, d_out, want, d_off, nullptr, d_work, work, s)))
-        return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out.p, want, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return DG_OK;
+    const auto launch = [&](uint8_t *d_out, uint64_t d_cap, uint64_t *d_off, uint8_t *d_status) {
+        return evals_launch(c, ep, dc.data(), WriteCall{n, 0, d_out, d_cap, d_off, d_status}, d_work, work, s);
+    };
+    return write_host_tail(s, n * K, out, cap, out_off, status, need, launch);
 }
 
 }  // extern "C"

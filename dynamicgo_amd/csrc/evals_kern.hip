@@ -56,7 +56,7 @@ __global__ __launch_bounds__(EV_BLOCK) void evals_emit_kernel(EVParams A)
     }
 }
 
-static dim3 cell_grid(const EVParams &A) { return dim3((uint32_t)((A.pairs + EV_BLOCK - 1) / EV_BLOCK)); }
+static_assert(EV_BLOCK == VL_BLOCK, "cell_grid (vals_device.h) counts in blocks of VL_BLOCK");
 
 void launch_evals_entry_size(hipStream_t s, const dg_eval_col &c, uint32_t kt, uint32_t vt, uint32_t *elen)
 {
@@ -64,11 +64,11 @@ void launch_evals_entry_size(hipStream_t s, const dg_eval_col &c, uint32_t kt, u
                        c.d_key_len, c.d_val_len, c.n_ent, kt, vt, elen);
 }
 
-void launch_evals_cells(hipStream_t s, const EVParams &A) { hipLaunchKernelGGL(evals_cell_kernel, cell_grid(A), dim3(EV_BLOCK), 0, s, A); }
+void launch_evals_cells(hipStream_t s, const EVParams &A) { hipLaunchKernelGGL(evals_cell_kernel, cell_grid(A.pairs), dim3(EV_BLOCK), 0, s, A); }
 
 void launch_evals_emit(hipStream_t s, const EVParams &A, uint32_t blocks)
 {
-    hipLaunchKernelGGL(evals_head_kernel, cell_grid(A), dim3(EV_BLOCK), 0, s, A);
+    hipLaunchKernelGGL(evals_head_kernel, cell_grid(A.pairs), dim3(EV_BLOCK), 0, s, A);
     if (blocks) hipLaunchKernelGGL(evals_emit_kernel, dim3(blocks), dim3(EV_BLOCK), 0, s, A);
 }
 

@@ -492,24 +492,6 @@ struct dg_rows : PlanRec {
     dg_path_hdr sub_hdr;
 };
 
-/* a value plan (vals_host.hip): K kinds and, in struct mode, K field ids */
-struct dg_vals {
-    dg_ctx *ctx;
-    uint32_t K;
-    bool ids, scalars; /* struct mode; no STRING, list or set column */
-    uint8_t kinds[DG_VALS_MAX_COLS];
-    int16_t field_ids[DG_VALS_MAX_COLS];
-};
-
-/* an entry-value plan (evals_host.hip): K container kinds and, in struct mode, K field ids */
-struct dg_evals {
-    dg_ctx *ctx;
-    uint32_t K;
-    bool ids;
-    uint16_t kinds[DG_VALS_MAX_COLS];
-    int16_t field_ids[DG_VALS_MAX_COLS];
-};
-
 /* one batch of messages (device pointers) and where the lookup's records go */
 struct TGetBatch {
     const uint8_t *src;

@@ -140,6 +140,22 @@ TGI uint64_t vl_flush(VLBytes &h, uint8_t *out, uint64_t at, uint64_t cap)
     return at;
 }
 
+/* the 3-byte field header of struct mode (fh): the wire type and the id big-endian */
+TGI void vl_field(VLBytes &h, uint32_t fh, uint32_t wire, int32_t id)
+{
+    if (fh) vl_push(h, (uint64_t)wire | (uint64_t)__builtin_bswap16((uint16_t)id) << 8, 3);
+}
+
+/* The item of len bytes at out + pos closed, h holding what precedes its body: STOP goes with h when nothing lies
+ * between (a near stop), else behind the body (a far stop); nothing is stored at cap or beyond. */
+TGI void vl_close(VLBytes &h, uint32_t stop, uint32_t len, uint8_t *out, uint64_t pos, uint64_t cap)
+{
+    const bool far_stop = stop && len != h.n + 1;
+    if (stop && !far_stop) vl_push(h, 0, 1);
+    (void)vl_flush(h, out, pos, cap);
+    if (far_stop && pos + len - 1 < cap) out[pos + len - 1] = 0;
+}
+
 /* what precedes the body of the item z at out + pos, a scalar's bytes (v) and
  * the STOP byte, nothing of it at cap or beyond */
 TGI void vl_head(uint32_t kind, int32_t id, uint32_t fh, uint32_t stop, const VLSize &z, uint64_t v, uint8_t *out,
@@ -147,15 +163,12 @@ TGI void vl_head(uint32_t kind, int32_t id, uint32_t fh, uint32_t stop, const VL
 {
     VLBytes h{0, 0, 0};
     if (z.present) {
-        if (fh) vl_push(h, (uint64_t)vl_wire(kind) | (uint64_t)__builtin_bswap16((uint16_t)id) << 8, 3);
+        vl_field(h, fh, vl_wire(kind), id);
         if (kind & VL_CONTAINER) vl_push(h, (uint64_t)(kind & 0x3Fu) | (uint64_t)__builtin_bswap32((uint32_t)z.cnt) << 8, 5);
         else if (kind == TT_STRING) vl_push(h, __builtin_bswap32((uint32_t)z.cnt), 4);
         else vl_push(h, vl_scalar(kind, v), tg_fixed(kind));
     }
-    const bool far_stop = stop && z.len != h.n + 1; /* a body lies between */
-    if (stop && !far_stop) vl_push(h, 0, 1);
-    (void)vl_flush(h, out, pos, cap);
-    if (far_stop && pos + z.len - 1 < cap) out[pos + z.len - 1] = 0;
+    vl_close(h, stop, z.len, out, pos, cap);
 }
 
 /* unit u of a body of cnt bytes (STRING, from pay) or cnt elements (a
@@ -189,29 +202,42 @@ TGI uint64_t vl_units(uint32_t kind, uint64_t cnt)
     return (bytes + VL_UNIT - 1) / VL_UNIT;
 }
 
-/* cell q decoded from the inputs */
-struct VLPair {
+/* Cell q of either parameter record (VLParams; EVParams, evals_device.h): fh = 3 in struct mode, stop = 1 behind a
+ * message's last item, present: the inputs hold a value for it */
+struct VLCell {
     uint32_t i, j, kind, fh, stop;
     int32_t id;
+    bool present;
+};
+template <class P>
+TGI VLCell vl_cell(const P &A, uint64_t q)
+{
+    VLCell p;
+    p.i = (uint32_t)q / A.K, p.j = (uint32_t)q - p.i * A.K;
+    p.kind = A.kinds[p.j], p.id = A.ids[p.j];
+    p.fh = A.has_ids ? 3u : 0u, p.stop = A.has_ids && p.j == A.K - 1;
+    p.present = !(A.has_ids && A.col[p.j].d_present) || A.col[p.j].d_present[p.i] != 0;
+    return p;
+}
+
+/* a cell of vals with its item */
+struct VLPair : VLCell {
     VLSize z;
     uint64_t v; /* a scalar's value; a string's payload offset */
 };
 TGI VLPair vl_pair(const VLParams &A, uint64_t q)
 {
     VLPair p;
-    p.i = (uint32_t)q / A.K, p.j = (uint32_t)q - p.i * A.K;
-    p.kind = A.kinds[p.j], p.id = A.ids[p.j];
-    p.fh = A.has_ids ? 3u : 0u, p.stop = A.has_ids && p.j == A.K - 1;
+    static_cast<VLCell &>(p) = vl_cell(A, q);
     const dg_val_col &c = A.col[p.j];
-    const bool present = !(A.has_ids && c.d_present) || c.d_present[p.i] != 0;
     uint64_t cnt = 0;
     p.v = 0;
-    if (present) {
+    if (p.present) {
         if (p.kind & VL_CONTAINER) cnt = c.d_elem_off[p.i + 1] - c.d_elem_off[p.i];
         else p.v = c.d_val[p.i];
         if (p.kind == TT_STRING) cnt = c.d_len[p.i];
     }
-    p.z = vl_size(p.kind, p.fh, p.stop, present, cnt);
+    p.z = vl_size(p.kind, p.fh, p.stop, p.present, cnt);
     return p;
 }
 
@@ -252,8 +278,10 @@ TGI void vl_granule(const VLParams &A, uint64_t lo, uint64_t hi, uint64_t p, uin
     }
 }
 
+inline dim3 cell_grid(uint64_t pairs) { return dim3((uint32_t)((pairs + VL_BLOCK - 1) / VL_BLOCK)); } /* one lane per cell */
+
 void launch_vals_size(hipStream_t s, const VLParams &A, bool closed);
-void launch_vals_rebase(hipStream_t s, const VLParams &A);
+void launch_vals_rebase(hipStream_t s, uint64_t *off, uint64_t entries, uint64_t base); /* evals' too */
 void launch_vals_emit(hipStream_t s, const VLParams &A, uint32_t max_blocks, bool lane_emit, bool bodies);
 
 }  // namespace dg

@@ -9,8 +9,8 @@
 
 /* the size and kind helpers of vals_device.h serve the host here too */
 #define TGI __host__ __device__ __forceinline__
-#include "host_internal.h"
 #include "vals_device.h"
+#include "write_internal.h"
 
 using namespace dg;
 
@@ -18,37 +18,26 @@ using namespace dg;
  * tile sums are the component's own, one set per context: a launch on another
  * stream than the previous one waits for it (StreamOrder). A plan of scalars
  * with every field present takes neither: its offsets are a closed form. */
-static int vals_launch(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, uint64_t n, uint64_t out_base, uint8_t *d_out,
-                       uint64_t cap, uint64_t *d_out_off, uint8_t *d_status, hipStream_t s)
+static int vals_launch(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, const WriteCall &w, hipStream_t s)
 {
     const uint32_t K = vp->K;
-    if (!cols) return set_err(DG_E_INVALID, "null columns");
+    int rc = write_prologue(vp, cols, w);
+    if (rc || !w.n) return rc;
     bool closed = vp->scalars;
     for (uint32_t k = 0; k < K; k++) {
         const dg_val_col &v = cols[k];
         const uint32_t kind = vp->kinds[k];
-        if (v.d_present && !vp->ids) return set_err(DG_E_ARG, "column %u: d_present in a plan without field ids", k);
         if (v.d_present) closed = false;
-        if (n == 0) continue;
         /* d_elems and d_src may be null: a column of empty lists or empty strings reads neither */
         if (kind & VL_CONTAINER ? !v.d_elem_off : !v.d_val || (kind == TT_STRING && !v.d_len))
             return set_err(DG_E_INVALID, "column %u: null buffer", k);
         if (((uintptr_t)v.d_val & 7) || ((uintptr_t)v.d_elem_off & 7) || ((uintptr_t)v.d_elems & 7) || ((uintptr_t)v.d_len & 3))
             return set_err(DG_E_INVALID, "column %u: values, offsets or elements not aligned", k);
     }
-    if (n == 0) return DG_OK;
-    if (!d_out_off || ((uintptr_t)d_out_off & 7)) return set_err(DG_E_INVALID, "d_out_off null or not 8-byte aligned");
-    const uint64_t pairs = n * K;
-    if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
-        return set_err(DG_E_INVALID, "batch of %llu messages x %u columns", (unsigned long long)n, K);
     VLParams A;
-    memset(&A, 0, sizeof A);
-    memcpy(A.col, cols, K * sizeof *cols);
-    memcpy(A.kinds, vp->kinds, sizeof A.kinds);
-    memcpy(A.ids, vp->field_ids, sizeof A.ids);
-    A.K = K, A.has_ids = vp->ids, A.pairs = pairs, A.base = out_base, A.cap = cap;
-    A.off = d_out_off, A.status = d_status, A.out = d_out;
-    const bool emit = d_out && cap > out_base;
+    write_params(A, vp, cols, w);
+    const uint64_t pairs = A.pairs;
+    const bool emit = w.d_out && w.cap > w.out_base;
     const bool lane = c->knobs.vals_lane_emit == 1;
     const uint32_t max_blocks = (uint32_t)std::max(c->n_cu, 1) * 8u;
     if (closed) {
@@ -64,7 +53,6 @@ static int vals_launch(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, uin
         if (e != hipSuccess) return set_err(DG_E_HIP, "vals launch: %s", hipGetErrorString(e));
         return DG_OK;
     }
-    int rc;
     if ((rc = c->vals.grow(c->vals_len, pairs)) || (rc = c->vals.grow(c->vals_sums, (pairs + CL_SCAN_TILE - 1) / CL_SCAN_TILE)))
         return rc;
     HIPCHK(c->vals.acquire(s));
@@ -72,11 +60,11 @@ static int vals_launch(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, uin
     launch_vals_size(s, A, false);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
-        launch_cols_scan(s, A.len, pairs, c->vals_sums, d_out_off);
+        launch_cols_scan(s, A.len, pairs, c->vals_sums, w.d_out_off);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && out_base) {
-        launch_vals_rebase(s, A);
+    if (e == hipSuccess && w.out_base) {
+        launch_vals_rebase(s, w.d_out_off, pairs + 1, w.out_base);
         e = hipGetLastError();
     }
     if (e == hipSuccess && emit) {
@@ -92,18 +80,10 @@ extern "C" {
 
 int dg_vals_create(dg_ctx *c, const uint8_t *kinds, uint32_t K, const int16_t *field_ids, dg_vals **out)
 {
-    if (!c || !kinds || !out) return set_err(DG_E_INVALID, "null ctx/kinds/out");
-    if (K < 1 || K > DG_VALS_MAX_COLS) return set_err(DG_E_ARG, "%u columns (1 to %u)", K, DG_VALS_MAX_COLS);
-    std::unique_ptr<dg_vals> vp(new dg_vals());
-    memset(vp.get(), 0, sizeof(dg_vals));
-    vp->ctx = c, vp->K = K, vp->ids = field_ids != nullptr, vp->scalars = true;
-    for (uint32_t k = 0; k < K; k++) {
-        if (!vl_kind_ok(kinds[k])) return set_err(DG_E_ARG, "column %u: unknown kind %u", k, kinds[k]);
-        vp->kinds[k] = kinds[k];
-        vp->scalars &= vl_scalar_kind(kinds[k]);
-        if (field_ids) vp->field_ids[k] = field_ids[k];
-    }
-    *out = vp.release();
+    const int rc = write_plan_create(c, kinds, K, field_ids, [](uint32_t kind) { return vl_kind_ok(kind); }, out);
+    if (rc) return rc;
+    (*out)->scalars = true;
+    for (uint32_t k = 0; k < K; k++) (*out)->scalars &= vl_scalar_kind(kinds[k]);
     return DG_OK;
 }
 
@@ -118,21 +98,15 @@ int dg_vals_batch_device(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, u
 {
     Entry g(c, c && vp && vp->ctx == c, stream, "null ctx/plan, or a plan of another context");
     if (g.rc) return g.rc;
-    return vals_launch(c, vp, cols, n, out_base, d_out, cap, d_out_off, d_status, g.s);
+    return vals_launch(c, vp, cols, WriteCall{n, out_base, d_out, cap, d_out_off, d_status}, g.s);
 }
 
 int dg_vals_batch_host(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, uint64_t n, uint8_t *out, uint64_t cap,
                        uint64_t *out_off, uint8_t *status, uint64_t *need)
 {
-    if (!c || !vp || vp->ctx != c || !cols) return set_err(DG_E_INVALID, "null ctx/plan/columns, or a plan of another context");
+    int rc = write_host_prologue(c, vp, cols, n, out_off, need);
+    if (rc || !n) return rc;
     const uint32_t K = vp->K;
-    for (uint32_t k = 0; k < K; k++)
-        if (cols[k].d_present && !vp->ids) return set_err(DG_E_ARG, "column %u: d_present in a plan without field ids", k);
-    if (n == 0) return empty_batch(out_off, need);
-    if (!out_off) return set_err(DG_E_INVALID, "null buffer");
-    const uint64_t pairs = n * K;
-    if (n > 0xFFFFFFFFull || pairs > 0xFFFFFFFFull)
-        return set_err(DG_E_INVALID, "batch of %llu messages x %u columns", (unsigned long long)n, K);
     Entry g(c, true);
     if (g.rc) return g.rc;
     /* the inputs on the device: a string column's payloads from the first to
@@ -146,7 +120,6 @@ int dg_vals_batch_host(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, uin
     std::vector<ColDev> dev(K);
     std::vector<dg_val_col> dc(K);
     std::vector<uint64_t> tmp;
-    int rc;
     for (uint32_t k = 0; k < K; k++) {
         const dg_val_col &h = cols[k];
         const uint32_t kind = vp->kinds[k];
@@ -178,36 +151,17 @@ int dg_vals_batch_host(dg_ctx *c, const dg_vals *vp, const dg_val_col *cols, uin
             continue;
         }
         if (!h.d_len) return set_err(DG_E_INVALID, "column %u: null buffer", k);
-        uint64_t lo = ~0ull, hi = 0;
-        for (uint64_t i = 0; i < n; i++) {
-            if (!h.d_len[i] || h.d_len[i] > 0x7FFFFFFFu) continue;
-            lo = std::min(lo, h.d_val[i]), hi = std::max(hi, h.d_val[i] + h.d_len[i]);
-        }
-        if (hi <= lo) lo = hi = 0;
-        tmp.assign(h.d_val, h.d_val + n);
-        for (uint64_t i = 0; i < n; i++) tmp[i] = h.d_len[i] && h.d_len[i] <= 0x7FFFFFFFu ? tmp[i] - lo : 0;
-        if ((rc = to_device(dev[k].val, tmp.data(), n)) || (rc = to_device(dev[k].len, h.d_len, n)) ||
-            (rc = to_device(dev[k].src, h.d_src + lo, hi - lo, 16)))
+        const auto live = [&h](uint64_t i) { return h.d_len[i] <= 0x7FFFFFFFu; }; /* not flagged DG_VAL_E_SIZE */
+        if ((rc = payloads_to_device(h.d_val, h.d_len, h.d_src, n, live, dev[k].val, dev[k].src)) ||
+            (rc = to_device(dev[k].len, h.d_len, n)))
             return rc;
         dc[k].d_val = dev[k].val, dc[k].d_len = dev[k].len, dc[k].d_src = dev[k].src;
     }
-    DevArr<uint64_t> d_off;
-    DevArr<uint8_t> d_status, d_out;
-    if ((rc = d_off.alloc(pairs + 1)) || (rc = d_status.alloc(pairs))) return rc;
     const hipStream_t s = g.s;
-    if ((rc = vals_launch(c, vp, dc.data(), n, 0, nullptr, 0, d_off, d_status, s))) return rc; /* sizing */
-    HIPCHK(hipMemcpyAsync(out_off, d_off.p, (pairs + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (status) HIPCHK(hipMemcpyAsync(status, d_status.p, pairs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const uint64_t want = out_off[pairs];
-    if (need) *need = want;
-    if (!out && !cap) return DG_OK; /* sizing */
-    if (want > cap || (!out && want)) return set_err(DG_E_NOMEM, "values need %llu bytes", (unsigned long long)want);
-    if (!want) return DG_OK;
-    if ((rc = d_out.alloc(want + 16)) || (rc = vals_launch(c, vp, dc.data(), n, 0, d_out, want, d_off, nullptr, s))) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out.p, want, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return DG_OK;
+    const auto launch = [&](uint8_t *d_out, uint64_t d_cap, uint64_t *d_off, uint8_t *d_status) {
+        return vals_launch(c, vp, dc.data(), WriteCall{n, 0, d_out, d_cap, d_off, d_status}, s);
+    };
+    return write_host_tail(s, n * K, out, cap, out_off, status, need, launch);
 }
 
 }  // extern "C"

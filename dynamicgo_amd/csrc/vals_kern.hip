@@ -66,28 +66,24 @@ __global__ __launch_bounds__(VL_BLOCK) void vals_body_kernel(VLParams A)
     }
 }
 
-static dim3 cell_grid(const VLParams &A) { return dim3((uint32_t)((A.pairs + VL_BLOCK - 1) / VL_BLOCK)); }
-
 void launch_vals_size(hipStream_t s, const VLParams &A, bool closed)
 {
-    if (closed) hipLaunchKernelGGL(vals_size_kernel<true>, cell_grid(A), dim3(VL_BLOCK), 0, s, A);
-    else hipLaunchKernelGGL(vals_size_kernel<false>, cell_grid(A), dim3(VL_BLOCK), 0, s, A);
+    if (closed) hipLaunchKernelGGL(vals_size_kernel<true>, cell_grid(A.pairs), dim3(VL_BLOCK), 0, s, A);
+    else hipLaunchKernelGGL(vals_size_kernel<false>, cell_grid(A.pairs), dim3(VL_BLOCK), 0, s, A);
 }
 
-void launch_vals_rebase(hipStream_t s, const VLParams &A)
+void launch_vals_rebase(hipStream_t s, uint64_t *off, uint64_t entries, uint64_t base)
 {
-    const uint64_t entries = A.pairs + 1;
-    hipLaunchKernelGGL(vals_rebase_kernel, dim3((uint32_t)((entries + VL_BLOCK - 1) / VL_BLOCK)), dim3(VL_BLOCK), 0, s, A.off,
-                       entries, A.base);
+    hipLaunchKernelGGL(vals_rebase_kernel, cell_grid(entries), dim3(VL_BLOCK), 0, s, off, entries, base);
 }
 
 void launch_vals_emit(hipStream_t s, const VLParams &A, uint32_t max_blocks, bool lane_emit, bool bodies)
 {
     if (lane_emit) {
-        hipLaunchKernelGGL(vals_head_kernel<true>, cell_grid(A), dim3(VL_BLOCK), 0, s, A);
+        hipLaunchKernelGGL(vals_head_kernel<true>, cell_grid(A.pairs), dim3(VL_BLOCK), 0, s, A);
         return;
     }
-    hipLaunchKernelGGL(vals_head_kernel<false>, cell_grid(A), dim3(VL_BLOCK), 0, s, A);
+    hipLaunchKernelGGL(vals_head_kernel<false>, cell_grid(A.pairs), dim3(VL_BLOCK), 0, s, A);
     if (!bodies) return; /* a plan of scalars */
     /* no byte at cap or beyond is stored, so no more chunks than lie below cap */
     const uint64_t first = A.base & ~(uint64_t)(VL_UNIT - 1);

@@ -1492,43 +1492,57 @@ def val_kind(kind) -> int:
     return int(k)
 
 
-class ValuePlan(_Handle):
+class _WritePlan(_Handle):
+    """What ValuePlan and EntryValuePlan share: the constructor of a plan of kinds with optional field ids. A class
+    names the library's entries (_create, _count, _wire_type, _destroy, and _host, the host batch), the function that
+    resolves a kind (_kind), the kinds array's numpy dtype (_kind_dtype) and the column record with its pointer fields."""
+    _create = _count = _wire_type = _host = _kind = _kind_dtype = _rec = _fields = None
+
+    def __init__(self, kinds, field_ids=None, ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.kinds = [self._kind(k) for k in kinds]
+        self.field_ids = None if field_ids is None else [int(f) for f in field_ids]
+        if self.field_ids is not None and len(self.field_ids) != len(self.kinds):
+            raise ValueError("%d field ids for %d columns" % (len(self.field_ids), len(self.kinds)))
+        ids = None if self.field_ids is None else np.array(self.field_ids, dtype=np.int16)
+        lib, h = _lib.lib(), C.c_void_p()
+        _lib.check(getattr(lib, self._create)(self.ctx.h, np.array(self.kinds, dtype=self._kind_dtype).tobytes(),
+                                              len(self.kinds), None if ids is None else ids.ctypes.data, C.byref(h)))
+        self.h = h
+        self.count = int(getattr(lib, self._count)(h))
+        self.wire_types = [int(getattr(lib, self._wire_type)(h, k)) for k in range(self.count)]
+
+    def _cols(self, cols):
+        """_rec[K] from per-column dicts (or tuples in _fields' order) of tensors, arrays or raw pointers and the int n_ent"""
+        if len(cols) != self.count:
+            raise ValueError("%d columns for a plan of %d" % (len(cols), self.count))
+        recs = (self._rec * self.count)()
+        for r, c in zip(recs, cols):
+            c = c if isinstance(c, dict) else dict(zip(self._fields, c))
+            for f in self._fields:
+                x = c.get(f)
+                setattr(r, f, x.ctypes.data if isinstance(x, np.ndarray) else _ptr(x))
+            if hasattr(r, "n_ent"):
+                r.n_ent = int(c["n_ent"])
+        return recs
+
+
+class ValuePlan(_WritePlan):
     """1 to 16 columns to write, each a kind (val_kind), on one context's
     device (dg_vals). With `field_ids` (one int16 per column) the plan builds
     struct messages: every item gets its field header and every message its
     STOP; without, the items are bare values, what edit_many_device takes.
     .wire_types: the columns' wire types (edit_many_device's val_types)."""
-    _destroy = "dg_vals_destroy"
-
-    def __init__(self, kinds, field_ids=None, ctx: Optional[Context] = None):
-        self.ctx = ctx or default_context()
-        self.kinds = [val_kind(k) for k in kinds]
-        self.field_ids = None if field_ids is None else [int(f) for f in field_ids]
-        if self.field_ids is not None and len(self.field_ids) != len(self.kinds):
-            raise ValueError("%d field ids for %d columns" % (len(self.field_ids), len(self.kinds)))
-        ids = None if self.field_ids is None else np.array(self.field_ids, dtype=np.int16)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().dg_vals_create(self.ctx.h, bytes(self.kinds), len(self.kinds),
-                                             None if ids is None else ids.ctypes.data, C.byref(h)))
-        self.h = h
-        self.count = int(_lib.lib().dg_vals_count(h))
-        self.wire_types = [int(_lib.lib().dg_vals_wire_type(h, k)) for k in range(self.count)]
+    _create, _count, _wire_type, _destroy = "dg_vals_create", "dg_vals_count", "dg_vals_wire_type", "dg_vals_destroy"
+    _host, _kind, _kind_dtype = "dg_vals_batch_host", staticmethod(val_kind), np.uint8
+    _rec, _fields = _lib.ValCol, ("val", "len", "src", "elem_off", "elems", "present")
 
 
-_VAL_FIELDS = ("val", "len", "src", "elem_off", "elems", "present")
-
-
-def _val_cols(cols, count: int):
-    """dg_val_col[K] from per-column dicts (or tuples in _VAL_FIELDS' order) of tensors, arrays or raw pointers"""
-    if len(cols) != count:
-        raise ValueError("%d columns for a plan of %d" % (len(cols), count))
-    recs = (_lib.ValCol * count)()
-    for r, c in zip(recs, cols):
-        c = c if isinstance(c, dict) else dict(zip(_VAL_FIELDS, c))
-        for f in _VAL_FIELDS:
-            x = c.get(f)
-            setattr(r, f, x.ctypes.data if isinstance(x, np.ndarray) else _ptr(x))
-    return recs
+def _device_call(out, out_off, cap, stream):
+    """(the stream's handle, cap) of a *_device write: cap defaults to out's size less 16, 0 without out"""
+    if cap is None:
+        cap = int(out.numel()) - 16 if hasattr(out, "numel") else 0
+    return _stream_handle(stream, out_off), max(cap, 0)
 
 
 def values_device(plan: ValuePlan, cols, n: int, out, out_off, status=None, out_base: int = 0, cap: Optional[int] = None,
@@ -1543,11 +1557,24 @@ def values_device(plan: ValuePlan, cols, n: int, out, out_off, status=None, out_
     offsets (sizing); out_off int64[n * K + 1]; status uint8[n * K] or None.
     cap defaults to out's size less 16. What it fills is what
     edit_many_device takes as val / val_off. Asynchronous on `stream`."""
-    s = _stream_handle(stream, out_off)
-    if cap is None:
-        cap = int(out.numel()) - 16 if hasattr(out, "numel") else 0
-    _lib.check(_lib.lib().dg_vals_batch_device(plan.ctx.h, plan.h, _val_cols(cols, plan.count), n, out_base, _ptr(out),
-                                               max(cap, 0), _ptr(out_off), _ptr(status), s))
+    s, cap = _device_call(out, out_off, cap, stream)
+    _lib.check(_lib.lib().dg_vals_batch_device(plan.ctx.h, plan.h, plan._cols(cols), n, out_base, _ptr(out), cap,
+                                               _ptr(out_off), _ptr(status), s))
+
+
+def _pack_strings(rows):
+    """str / bytes -> (offsets uint64, lengths uint32, the payloads back to back with 16 spare bytes)"""
+    pay = [x.encode() if isinstance(x, str) else bytes(x) for x in rows]
+    lens = np.fromiter((len(x) for x in pay), dtype=np.uint64, count=len(pay))
+    return (np.cumsum(lens) - lens).astype(np.uint64), lens.astype(np.uint32), \
+        np.frombuffer(b"".join(pay) + b"\0" * 16, dtype=np.uint8)
+
+
+def _present_col(present, n: int) -> np.ndarray:
+    p = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+    if len(p) != n:
+        raise ValueError("present of %d entries for %d messages" % (len(p), n))
+    return p
 
 
 def _host_column(kind: int, column, n: int, present=None):
@@ -1563,17 +1590,11 @@ def _host_column(kind: int, column, n: int, present=None):
         flat = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
         c["elem_off"], c["elems"] = off, _as_u64(flat, kind & 0x3F)
     elif kind == VAL_STR:
-        rows = [x.encode() if isinstance(x, str) else bytes(x) for x in column]
-        lens = np.fromiter((len(x) for x in rows), dtype=np.uint64, count=n)
-        c["val"] = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if n else np.zeros(0, dtype=np.uint64)
-        c["len"] = lens.astype(np.uint32)
-        c["src"] = np.frombuffer(b"".join(rows) + b"\0" * 16, dtype=np.uint8)
+        c["val"], c["len"], c["src"] = _pack_strings(column)
     else:
         c["val"] = _as_u64(np.asarray(column, dtype=np.float64 if kind == VAL_F64 else None), kind)
     if present is not None:
-        c["present"] = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
-        if len(c["present"]) != n:
-            raise ValueError("present of %d entries for %d messages" % (len(c["present"]), n))
+        c["present"] = _present_col(present, n)
     return c
 
 
@@ -1592,22 +1613,58 @@ def _as_u64(a: np.ndarray, elem: int) -> np.ndarray:
     return np.ascontiguousarray(a.astype(np.int64) if a.dtype.kind == "i" else a.astype(np.uint64)).view(np.uint64)
 
 
-def _values_host(plan: ValuePlan, cols, n: int):
-    lib = _lib.lib()
+def _write_host(plan: _WritePlan, cols, n: int):
+    """the plan's host entry over host columns: (arena, off, status)"""
     k = plan.count
     off = np.zeros(n * k + 1, dtype=np.uint64)
     status = np.zeros(n * k, dtype=np.uint8)
     need = C.c_uint64(0)
-    recs = _val_cols(cols, k)
-
+    recs = plan._cols(cols)
     for sized in (False, True):  # the first call sizes: the arena's bytes are known exactly after it
         cap = int(need.value) if sized else 0
         out = np.zeros(cap, dtype=np.uint8)
-        _lib.check(lib.dg_vals_batch_host(plan.ctx.h, plan.h, recs, n, out.ctypes.data if cap else None, cap,
-                                          off.ctypes.data, status.ctypes.data, C.byref(need)))
+        _lib.check(getattr(_lib.lib(), plan._host)(plan.ctx.h, plan.h, recs, n, out.ctypes.data if cap else None, cap,
+                                                   off.ctypes.data, status.ctypes.data, C.byref(need)))
         if not need.value:
             break
     return out, off, status
+
+
+_values_host = _entry_values_host = _write_host  # the names the two components' tests call it by
+
+
+def _write_batch(cls, host_col, columns, plan, ctx):
+    """values_batch / entry_values_batch: cls the plan class, host_col its host-column function"""
+    wp = plan if isinstance(plan, cls) else cls(plan, None, ctx)
+    with _unless_given(wp, plan):
+        if len(columns) != wp.count:
+            raise ValueError("%d columns for a plan of %d" % (len(columns), wp.count))
+        n = len(columns[0])
+        return _write_host(wp, [host_col(k, c, n) for k, c in zip(wp.kinds, columns)], n)
+
+
+def _set_write_columns(cls, host_col, msgs, parent, columns, desc, root_type, ctx):
+    """set_columns_batch / set_entry_columns_batch"""
+    columns = list(columns)
+    if not 1 <= len(columns) <= EDITM_MAX_ITEMS:
+        raise ValueError("%d columns (1 to %d)" % (len(columns), EDITM_MAX_ITEMS))
+    with cls([c[1] for c in columns], None, ctx) as wp:
+        if any(len(c[2]) != len(msgs) for c in columns):
+            raise ValueError("a column's length is not the batch's")
+        arena, off, _ = _write_batch(cls, host_col, [c[2] for c in columns], wp, None) if msgs else \
+            (np.zeros(0, np.uint8), np.zeros(1, np.uint64), None)
+        with EditManyPlan(parent, [c[0] for c in columns], EDIT_SET, desc, ctx) as plan:
+            return _editm_batch(msgs, plan, None, wp.wire_types, root_type, encoded=(arena, off))
+
+
+def _build_write_structs(cls, host_col, fields, ctx):
+    """build_structs_batch / build_entry_structs_batch"""
+    fields = [tuple(f) for f in fields]
+    n = len(fields[0][2])
+    with cls([f[1] for f in fields], [f[0] for f in fields], ctx) as wp:
+        cols = [host_col(k, f[2], n, f[3] if len(f) > 3 else None) for k, f in zip(wp.kinds, fields)]
+        arena, off, _ = _write_host(wp, cols, n)
+        return _split(arena, off[::wp.count])
 
 
 def values_batch(columns, plan, ctx: Optional[Context] = None):
@@ -1618,12 +1675,7 @@ def values_batch(columns, plan, ctx: Optional[Context] = None):
     written at the kind's width. Returns (arena uint8, off uint64[n * K + 1],
     status uint8[n * K]), message-major: item j of message i is
     arena[off[i * K + j]:off[i * K + j + 1]]."""
-    vp = plan if isinstance(plan, ValuePlan) else ValuePlan(plan, None, ctx)
-    with _unless_given(vp, plan):
-        if len(columns) != vp.count:
-            raise ValueError("%d columns for a plan of %d" % (len(columns), vp.count))
-        n = len(columns[0])
-        return _values_host(vp, [_host_column(k, c, n) for k, c in zip(vp.kinds, columns)], n)
+    return _write_batch(ValuePlan, _host_column, columns, plan, ctx)
 
 
 def set_columns_batch(msgs: Sequence[bytes], parent, columns, desc=None, root_type: int = STRUCT,
@@ -1632,27 +1684,14 @@ def set_columns_batch(msgs: Sequence[bytes], parent, columns, desc=None, root_ty
     column) sets the child at `step` of message i to column[i] encoded as
     `kind` (values_batch, then set_many_batch's host entry with the kinds'
     wire types). At most EDITM_MAX_ITEMS columns."""
-    columns = list(columns)
-    if not 1 <= len(columns) <= EDITM_MAX_ITEMS:
-        raise ValueError("%d columns (1 to %d)" % (len(columns), EDITM_MAX_ITEMS))
-    with ValuePlan([c[1] for c in columns], None, ctx) as vp:
-        if any(len(c[2]) != len(msgs) for c in columns):
-            raise ValueError("a column's length is not the batch's")
-        arena, off, _ = values_batch([c[2] for c in columns], vp) if msgs else (np.zeros(0, np.uint8), np.zeros(1, np.uint64), None)
-        with EditManyPlan(parent, [c[0] for c in columns], EDIT_SET, desc, ctx) as plan:
-            return _editm_batch(msgs, plan, None, vp.wire_types, root_type, encoded=(arena, off))
+    return _set_write_columns(ValuePlan, _host_column, msgs, parent, columns, desc, root_type, ctx)
 
 
 def build_structs_batch(fields, ctx: Optional[Context] = None) -> List[bytes]:
     """NewNodeStruct for a batch: `fields` is a list of (field_id, kind,
     column[, present]); message i holds, in the order given, every field whose
     present[i] is true (all, without present), then STOP."""
-    fields = [tuple(f) for f in fields]
-    n = len(fields[0][2])
-    with ValuePlan([f[1] for f in fields], [f[0] for f in fields], ctx) as vp:
-        cols = [_host_column(k, f[2], n, f[3] if len(f) > 3 else None) for k, f in zip(vp.kinds, fields)]
-        arena, off, _ = _values_host(vp, cols, n)
-        return _split(arena, off[::vp.count])
+    return _build_write_structs(ValuePlan, _host_column, fields, ctx)
 
 
 # ---------------------------------------------------------------------------
@@ -1701,27 +1740,14 @@ def _eval_types(kind: int):
     return (kind >> 4 & 15, kind & 15) if kind & EVAL_MAP else (0, VAL_STR)
 
 
-class EntryValuePlan(_Handle):
+class EntryValuePlan(_WritePlan):
     """1 to 16 container columns to write, each a kind (eval_kind), on one
     context's device (dg_evals). With `field_ids` the plan builds struct
     messages, as ValuePlan does. .wire_types: the columns' wire types
     (edit_many_device's val_types)."""
-    _destroy = "dg_evals_destroy"
-
-    def __init__(self, kinds, field_ids=None, ctx: Optional[Context] = None):
-        self.ctx = ctx or default_context()
-        self.kinds = [eval_kind(k) for k in kinds]
-        self.field_ids = None if field_ids is None else [int(f) for f in field_ids]
-        if self.field_ids is not None and len(self.field_ids) != len(self.kinds):
-            raise ValueError("%d field ids for %d columns" % (len(self.field_ids), len(self.kinds)))
-        ids = None if self.field_ids is None else np.array(self.field_ids, dtype=np.int16)
-        kk = np.array(self.kinds, dtype=np.uint16)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().dg_evals_create(self.ctx.h, kk.ctypes.data, len(self.kinds),
-                                              None if ids is None else ids.ctypes.data, C.byref(h)))
-        self.h = h
-        self.count = int(_lib.lib().dg_evals_count(h))
-        self.wire_types = [int(_lib.lib().dg_evals_wire_type(h, k)) for k in range(self.count)]
+    _create, _count, _wire_type, _destroy = "dg_evals_create", "dg_evals_count", "dg_evals_wire_type", "dg_evals_destroy"
+    _host, _kind, _kind_dtype = "dg_evals_batch_host", staticmethod(eval_kind), np.uint16
+    _rec, _fields = _lib.EvalCol, ("ent_off", "key", "key_len", "val", "val_len", "key_src", "val_src", "present")
 
     def work_bytes(self, n: int, n_ent) -> int:
         """the bytes of `work` entry_values_device needs for n messages whose column k holds n_ent[k] entries"""
@@ -1729,22 +1755,6 @@ class EntryValuePlan(_Handle):
         if len(ne) != self.count:
             raise ValueError("%d entry counts for a plan of %d" % (len(ne), self.count))
         return max(int(_lib.lib().dg_evals_work_bytes(self.h, n, ne.ctypes.data)), 8)
-
-
-_EVAL_FIELDS = ("ent_off", "key", "key_len", "val", "val_len", "key_src", "val_src", "present")
-
-
-def _eval_cols(cols, count: int):
-    """dg_eval_col[K] from per-column dicts of tensors, arrays or raw pointers and the int n_ent"""
-    if len(cols) != count:
-        raise ValueError("%d columns for a plan of %d" % (len(cols), count))
-    recs = (_lib.EvalCol * count)()
-    for r, c in zip(recs, cols):
-        for f in _EVAL_FIELDS:
-            x = c.get(f)
-            setattr(r, f, x.ctypes.data if isinstance(x, np.ndarray) else _ptr(x))
-        r.n_ent = int(c["n_ent"])
-    return recs
 
 
 def entry_values_device(plan: EntryValuePlan, cols, n: int, out, out_off, work, status=None, out_base: int = 0,
@@ -1759,12 +1769,10 @@ def entry_values_device(plan: EntryValuePlan, cols, n: int, out, out_off, work, 
     uint8[cap + 16] or None (sizing); out_off int64[n * K + 1]; status uint8[n
     * K] or None; work a uint8 tensor of plan.work_bytes(n, [n_ent...]) bytes,
     this call's alone until it has run. Asynchronous on `stream`."""
-    s = _stream_handle(stream, out_off)
-    if cap is None:
-        cap = int(out.numel()) - 16 if hasattr(out, "numel") else 0
+    s, cap = _device_call(out, out_off, cap, stream)
     wb = int(work.numel()) * int(work.element_size()) if hasattr(work, "numel") else plan.work_bytes(n, [c["n_ent"] for c in cols])
-    _lib.check(_lib.lib().dg_evals_batch_device(plan.ctx.h, plan.h, _eval_cols(cols, plan.count), n, out_base, _ptr(out),
-                                                max(cap, 0), _ptr(out_off), _ptr(status), _ptr(work), wb, s))
+    _lib.check(_lib.lib().dg_evals_batch_device(plan.ctx.h, plan.h, plan._cols(cols), n, out_base, _ptr(out), cap,
+                                                _ptr(out_off), _ptr(status), _ptr(work), wb, s))
 
 
 def _host_entry_column(kind: int, column, n: int, present=None):
@@ -1783,37 +1791,14 @@ def _host_entry_column(kind: int, column, n: int, present=None):
         if not t:
             continue
         if t == VAL_STR:
-            pay = [e[x].encode() if isinstance(e[x], str) else bytes(e[x]) for e in flat]
-            lens = np.fromiter((len(p) for p in pay), dtype=np.uint64, count=len(pay))
-            c[side] = (np.cumsum(lens) - lens).astype(np.uint64)
-            c[side + "_len"] = lens.astype(np.uint32)
-            c[side + "_src"] = np.frombuffer(b"".join(pay) + b"\0" * 16, dtype=np.uint8)
+            c[side], c[side + "_len"], c[side + "_src"] = _pack_strings(e[x] for e in flat)
         else:
             vals = [e[x] for e in flat]
             c[side] = _as_u64(np.asarray(vals, dtype=np.float64 if t == VAL_F64 else None), t) if vals else \
                 np.zeros(0, dtype=np.uint64)
     if present is not None:
-        c["present"] = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
-        if len(c["present"]) != n:
-            raise ValueError("present of %d entries for %d messages" % (len(c["present"]), n))
+        c["present"] = _present_col(present, n)
     return c
-
-
-def _entry_values_host(plan: EntryValuePlan, cols, n: int):
-    lib = _lib.lib()
-    k = plan.count
-    off = np.zeros(n * k + 1, dtype=np.uint64)
-    status = np.zeros(n * k, dtype=np.uint8)
-    need = C.c_uint64(0)
-    recs = _eval_cols(cols, k)
-    for sized in (False, True):  # the first call sizes: the arena's bytes are known exactly after it
-        cap = int(need.value) if sized else 0
-        out = np.zeros(cap, dtype=np.uint8)
-        _lib.check(lib.dg_evals_batch_host(plan.ctx.h, plan.h, recs, n, out.ctypes.data if cap else None, cap,
-                                           off.ctypes.data, status.ctypes.data, C.byref(need)))
-        if not need.value:
-            break
-    return out, off, status
 
 
 def entry_values_batch(columns, plan, ctx: Optional[Context] = None):
@@ -1822,12 +1807,7 @@ def entry_values_batch(columns, plan, ctx: Optional[Context] = None):
     map column a sequence of dicts or of sequences of (key, value) pairs (pairs
     keep their order and their duplicates). Returns (arena uint8, off uint64[n
     * K + 1], status uint8[n * K]), message-major as values_batch's."""
-    ep = plan if isinstance(plan, EntryValuePlan) else EntryValuePlan(plan, None, ctx)
-    with _unless_given(ep, plan):
-        if len(columns) != ep.count:
-            raise ValueError("%d columns for a plan of %d" % (len(columns), ep.count))
-        n = len(columns[0])
-        return _entry_values_host(ep, [_host_entry_column(k, c, n) for k, c in zip(ep.kinds, columns)], n)
+    return _write_batch(EntryValuePlan, _host_entry_column, columns, plan, ctx)
 
 
 def set_entry_columns_batch(msgs: Sequence[bytes], parent, columns, desc=None, root_type: int = STRUCT,
@@ -1835,15 +1815,7 @@ def set_entry_columns_batch(msgs: Sequence[bytes], parent, columns, desc=None, r
     """SetMany from entry columns, the counterpart of set_columns_batch: below
     the node at `parent`, every (step, kind, column) sets the child at `step`
     of message i to column[i] encoded as the container `kind`."""
-    columns = list(columns)
-    if not 1 <= len(columns) <= EDITM_MAX_ITEMS:
-        raise ValueError("%d columns (1 to %d)" % (len(columns), EDITM_MAX_ITEMS))
-    with EntryValuePlan([c[1] for c in columns], None, ctx) as ep:
-        if any(len(c[2]) != len(msgs) for c in columns):
-            raise ValueError("a column's length is not the batch's")
-        arena, off, _ = entry_values_batch([c[2] for c in columns], ep) if msgs else (np.zeros(0, np.uint8), np.zeros(1, np.uint64), None)
-        with EditManyPlan(parent, [c[0] for c in columns], EDIT_SET, desc, ctx) as plan:
-            return _editm_batch(msgs, plan, None, ep.wire_types, root_type, encoded=(arena, off))
+    return _set_write_columns(EntryValuePlan, _host_entry_column, msgs, parent, columns, desc, root_type, ctx)
 
 
 def build_entry_structs_batch(fields, ctx: Optional[Context] = None) -> List[bytes]:
@@ -1851,9 +1823,4 @@ def build_entry_structs_batch(fields, ctx: Optional[Context] = None) -> List[byt
     is a list of (field_id, kind, column[, present]); message i holds, in the
     order given, every field whose present[i] is true (all, without present),
     then STOP."""
-    fields = [tuple(f) for f in fields]
-    n = len(fields[0][2])
-    with EntryValuePlan([f[1] for f in fields], [f[0] for f in fields], ctx) as ep:
-        cols = [_host_entry_column(k, f[2], n, f[3] if len(f) > 3 else None) for k, f in zip(ep.kinds, fields)]
-        arena, off, _ = _entry_values_host(ep, cols, n)
-        return _split(arena, off[::ep.count])
+    return _build_write_structs(EntryValuePlan, _host_entry_column, fields, ctx)
