@@ -37,7 +37,9 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_vals_create", "dg_vals_destroy", "dg_vals_count", "dg_vals_wire_type", "dg_vals_batch_device",
            "dg_vals_batch_host",
            "dg_evals_create", "dg_evals_destroy", "dg_evals_count", "dg_evals_wire_type", "dg_evals_work_bytes",
-           "dg_evals_batch_device", "dg_evals_batch_host"]
+           "dg_evals_batch_device", "dg_evals_batch_host",
+           "dg_rvals_create", "dg_rvals_destroy", "dg_rvals_count", "dg_rvals_wire_type", "dg_rvals_work_bytes",
+           "dg_rvals_batch_device", "dg_rvals_batch_host"]
 
 _lib = None
 
@@ -172,6 +174,13 @@ def lib() -> C.CDLL:
         "dg_evals_work_bytes": (u64, [vp, u64, vp]),
         "dg_evals_batch_device": (i32, [vp, vp, vp, u64, u64, vp, u64, vp, vp, vp, u64, vp]),
         "dg_evals_batch_host": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, P64]),
+        "dg_rvals_create": (i32, [vp, vp, u32, vp, C.c_uint8, C.POINTER(vp)]),
+        "dg_rvals_destroy": (None, [vp]),
+        "dg_rvals_count": (u32, [vp]),
+        "dg_rvals_wire_type": (C.c_uint8, [vp]),
+        "dg_rvals_work_bytes": (u64, [vp, u64, u64]),
+        "dg_rvals_batch_device": (i32, [vp, vp, vp, vp, u64, u64, u64, vp, u64, vp, vp, vp, vp, u64, vp]),
+        "dg_rvals_batch_host": (i32, [vp, vp, vp, vp, u64, u64, vp, u64, vp, vp, vp, P64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -28,12 +28,13 @@ UNITS = ("j2t_kern_wave.hip", "j2t_kern_wave5.hip", "j2t_kern_small.hip", "j2t_k
          "tget_kern.hip", "tget_host.hip", "cut_kern.hip", "cut_host.hip", "kids_kern.hip", "kids_host.hip",
          "editm_kern.hip", "editm_host.hip", "flat_image.hip", "cols_kern.hip", "cols_host.hip",
          "ents_kern.hip", "ents_host.hip", "rows_kern.hip", "rows_host.hip",
-         "vals_kern.hip", "vals_host.hip", "evals_kern.hip", "evals_host.hip")
+         "vals_kern.hip", "vals_host.hip", "evals_kern.hip", "evals_host.hip",
+         "rvals_kern.hip", "rvals_host.hip")
 HEADERS = ("j2t_small.h", "j2t_wave.h", "j2t_machine.h", "j2t_device.h", "j2t_fast.h", "dg_tables.h", "host_internal.h",
            "t2j_device.h", "t2j_tables.h", "j2t_flat.h", "t2j_wave.h", "tget_device.h", "cut_device.h", "edit_device.h",
            "kids_device.h", "editm_device.h", "flat_image.h", "host_layout.h", "cols_device.h", "ents_device.h",
            "vals_device.h", "evals_device.h", "fl_classify.h", "rows_device.h", "walk_kern.h", "scan_kern.h", "scan_defs.h", "plan_internal.h",
-           "write_internal.h")
+           "write_internal.h", "rvals_device.h")
 
 
 def source_hash(extra_flags=()) -> str:

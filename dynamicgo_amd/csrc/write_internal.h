@@ -1,6 +1,6 @@
-/* write_internal.h — what vals_host.hip and evals_host.hip share: the plan record and its making, the checks before a
- * launch's per-column ones, the filling of the kernel record's common fields, the payload upload and the two-pass tail of
- * the host entries. */
+/* write_internal.h — what vals_host.hip, evals_host.hip and rvals_host.hip share: the plan record and its making, the
+ * checks before a launch's per-column ones, the filling of the kernel record's common fields (vals and evals, whose
+ * cells are the messages'), the payload upload and the two-pass tail of the host entries. */
 #pragma once
 #include "host_internal.h"
 
@@ -60,21 +60,31 @@ int write_check_cols(const WritePlan *p, const Col *cols)
     return DG_OK;
 }
 
-inline int write_check_pairs(const WritePlan *p, uint64_t n)
+/* the cells fit the scan: n messages (vals, evals) or n rows (rvals) of K columns */
+inline int write_check_pairs(const WritePlan *p, uint64_t n, const char *unit = "messages")
 {
     const bool fits = n <= 0xFFFFFFFFull && n * p->K <= 0xFFFFFFFFull;
-    return fits ? DG_OK : set_err(DG_E_INVALID, "batch of %llu messages x %u columns", (unsigned long long)n, p->K);
+    return fits ? DG_OK : set_err(DG_E_INVALID, "batch of %llu %s x %u columns", (unsigned long long)n, unit, p->K);
 }
 
-/* what both launches check before their per-column buffers; n == 0 is DG_OK with nothing else looked at */
+/* the columns' owners when they are not the messages: rvals' rows */
+struct WriteRows {
+    uint64_t count;
+    const char *unit;
+};
+
+/* what the launches check before their per-column buffers; n == 0 is DG_OK with nothing else looked at. The cells are
+ * the messages' unless `rows` says whose they are. */
 template <class Col>
-int write_prologue(const WritePlan *p, const Col *cols, const WriteCall &w)
+int write_prologue(const WritePlan *p, const Col *cols, const WriteCall &w, const WriteRows *rows = nullptr)
 {
     if (!cols) return set_err(DG_E_INVALID, "null columns");
     if (int rc = write_check_cols(p, cols)) return rc;
     if (w.n == 0) return DG_OK;
     if (!w.d_out_off || ((uintptr_t)w.d_out_off & 7)) return set_err(DG_E_INVALID, "d_out_off null or not 8-byte aligned");
-    return write_check_pairs(p, w.n);
+    if (!rows) return write_check_pairs(p, w.n);
+    if (w.n > 0xFFFFFFFFull) return set_err(DG_E_INVALID, "batch of %llu messages", (unsigned long long)w.n);
+    return write_check_pairs(p, rows->count, rows->unit);
 }
 
 /* the fields VLParams and EVParams share, from the plan and the call; every other field 0 */
@@ -108,13 +118,16 @@ int payloads_to_device(const uint64_t *off, const uint32_t *len, const uint8_t *
 
 /* what a host entry does first; n == 0 is answered here (off[0] = 0, *need = 0) */
 template <class Col>
-int write_host_prologue(dg_ctx *c, const WritePlan *p, const Col *cols, uint64_t n, uint64_t *out_off, uint64_t *need)
+int write_host_prologue(dg_ctx *c, const WritePlan *p, const Col *cols, uint64_t n, uint64_t *out_off, uint64_t *need,
+                        const WriteRows *rows = nullptr)
 {
     if (!c || !p || p->ctx != c || !cols) return set_err(DG_E_INVALID, "null ctx/plan/columns, or a plan of another context");
     if (int rc = write_check_cols(p, cols)) return rc;
     if (n == 0) return empty_batch(out_off, need);
     if (!out_off) return set_err(DG_E_INVALID, "null buffer");
-    return write_check_pairs(p, n);
+    if (!rows) return write_check_pairs(p, n);
+    if (n > 0xFFFFFFFFull) return set_err(DG_E_INVALID, "batch of %llu messages", (unsigned long long)n);
+    return write_check_pairs(p, rows->count, rows->unit);
 }
 
 /* The tail of a host entry, the inputs staged: launch(d_out, cap, d_off, d_status) once for the sizes (d_out null),

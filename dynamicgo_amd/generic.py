@@ -1,6 +1,10 @@
-"""thrift/generic on the GPU. Typed column writes (the last part of this
-module: ValuePlan, values_batch, values_device, set_columns_batch,
-build_structs_batch: the NewNode* constructors over tensors), row columns
+"""thrift/generic on the GPU. Row column writes (the last part of this
+module: RowValuePlan, row_values_batch, row_values_device, set_rows_batch,
+build_row_lists_batch: NewNodeList / NewNodeSet of structs over row tensors),
+entry column writes (EntryValuePlan, entry_values_batch, entry_values_device),
+typed column writes (the part before them: ValuePlan, values_batch,
+values_device, set_columns_batch, build_structs_batch: the NewNode*
+constructors over tensors), row columns
 (RowPlan, rows_batch, rows_device, row_list_device: the fields of every element
 of a list as ragged tensors), entry columns
 (the part before them: EntryPlan, entries_batch, entries_device,
@@ -1824,3 +1828,148 @@ def build_entry_structs_batch(fields, ctx: Optional[Context] = None) -> List[byt
     order given, every field whose present[i] is true (all, without present),
     then STOP."""
     return _build_write_structs(EntryValuePlan, _host_entry_column, fields, ctx)
+
+
+# ---------------------------------------------------------------------------
+# Row column writes, the inverse of the row columns above: ragged row tensors
+# encoded to list<struct> and set<struct> values (NewNodeList / NewNodeSet over
+# []interface{} of map[FieldID]interface{}, thrift/generic/node.go:154-187;
+# dg_rvals_* in dgj2t.h)
+# ---------------------------------------------------------------------------
+class RowValuePlan(_WritePlan):
+    """The elements of a list<struct> (container "list" / 15) or set<struct>
+    ("set" / 14) to write: 1 to 16 columns, each a kind (val_kind) and a field
+    id, on one context's device (dg_rvals). A column is indexed by row; message
+    i owns the rows [row_off[i], row_off[i + 1]). .wire_type: the wire type of
+    every message's item (edit_many_device's val_types entry)."""
+    _create, _count, _wire_type, _destroy = "dg_rvals_create", "dg_rvals_count", "dg_rvals_wire_type", "dg_rvals_destroy"
+    _host, _kind, _kind_dtype = "dg_rvals_batch_host", staticmethod(val_kind), np.uint8
+    _rec, _fields = _lib.ValCol, ("val", "len", "src", "elem_off", "elems", "present")
+
+    def __init__(self, kinds, field_ids, container="list", ctx: Optional[Context] = None):
+        self.ctx = ctx or default_context()
+        self.kinds = [self._kind(k) for k in kinds]
+        if field_ids is None:
+            raise ValueError("field ids are required: the elements are structs")
+        self.field_ids = [int(f) for f in field_ids]
+        if len(self.field_ids) != len(self.kinds):
+            raise ValueError("%d field ids for %d columns" % (len(self.field_ids), len(self.kinds)))
+        container = {"list": LIST, "set": SET}.get(container, container)
+        if not isinstance(container, int) or not 0 <= container <= 255:
+            raise ValueError("unknown container %r" % (container,))
+        ids = np.array(self.field_ids, dtype=np.int16)
+        lib, h = _lib.lib(), C.c_void_p()
+        _lib.check(lib.dg_rvals_create(self.ctx.h, np.array(self.kinds, dtype=np.uint8).tobytes(), len(self.kinds),
+                                       ids.ctypes.data, container, C.byref(h)))
+        self.h = h
+        self.count = int(lib.dg_rvals_count(h))
+        self.wire_type = int(lib.dg_rvals_wire_type(h))
+        self.wire_types = [self.wire_type]  # one item per message
+
+    def work_bytes(self, n: int, n_rows: int) -> int:
+        """the bytes of `work` that row_values_device needs for n messages over n_rows rows"""
+        return max(int(_lib.lib().dg_rvals_work_bytes(self.h, n, n_rows)), 8)
+
+
+def row_values_device(plan: RowValuePlan, cols, row_off, n: int, n_rows: int, out, out_off, work, status=None,
+                      cell_status=None, out_base: int = 0, cap: Optional[int] = None, stream=None):
+    """Device-resident batch (dg_rvals_batch_device) over torch tensors or raw
+    device pointers. row_off int64[n + 1] (rows_device's); cols: one dict per
+    column, indexed by row, in the shapes rows_device / row_list_device write:
+    val int64[n_rows], len int32[n_rows] and src uint8 (str; 16 spare bytes),
+    elem_off int64[n_rows + 1] and elems int64 (lists and sets), present
+    uint8[n_rows] (optional). n_rows is an int: no read-back. out uint8[cap +
+    16] or None (sizing); out_off int64[n + 1]; status uint8[n] and cell_status
+    uint8[n_rows * K] or None; work a uint8 tensor of plan.work_bytes(n, n_rows)
+    bytes, this call's alone until it has run. What it fills is what
+    edit_many_device takes as val / val_off for one item of plan.wire_type.
+    Asynchronous on `stream`."""
+    s, cap = _device_call(out, out_off, cap, stream)
+    wb = int(work.numel()) * int(work.element_size()) if hasattr(work, "numel") else plan.work_bytes(n, n_rows)
+    _lib.check(_lib.lib().dg_rvals_batch_device(plan.ctx.h, plan.h, plan._cols(cols), _ptr(row_off), n, n_rows, out_base,
+                                                _ptr(out), cap, _ptr(out_off), _ptr(status), _ptr(cell_status), _ptr(work),
+                                                wb, s))
+
+
+def _row_values_host(plan: RowValuePlan, cols, row_off, n: int, n_rows: int):
+    """the host entry over host columns: (arena, off[n + 1], status[n], cell_status[n_rows * K])"""
+    off = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint8)
+    cell_status = np.zeros(n_rows * plan.count, dtype=np.uint8)
+    row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+    need = C.c_uint64(0)
+    recs = plan._cols(cols)
+    out = np.zeros(0, dtype=np.uint8)
+    for sized in (False, True):  # the first call sizes: the arena's bytes are known exactly after it
+        cap = int(need.value) if sized else 0
+        out = np.zeros(cap, dtype=np.uint8)
+        _lib.check(_lib.lib().dg_rvals_batch_host(plan.ctx.h, plan.h, recs, row_off.ctypes.data, n, n_rows,
+                                                  out.ctypes.data if cap else None, cap, off.ctypes.data, status.ctypes.data,
+                                                  cell_status.ctypes.data, C.byref(need)))
+        if not need.value:
+            break
+    return out, off, status, cell_status
+
+
+def _rows_as_columns(plan: RowValuePlan, rows):
+    """per message a list of rows, a row a tuple in column order with None for an absent field -> (cols, row_off, n_rows)"""
+    flat = [tuple(r) for m in rows for r in m]
+    if any(len(r) != plan.count for r in flat):
+        raise ValueError("a row's length is not the plan's %d columns" % plan.count)
+    row_off = np.zeros(len(rows) + 1, dtype=np.uint64)
+    np.cumsum([len(m) for m in rows], out=row_off[1:])
+    if not flat:  # every list is empty: no per-row array is read, and none is made (an empty column has no dtype)
+        return [{} for _ in plan.kinds], row_off, 0
+    cols = []
+    for j, kind in enumerate(plan.kinds):
+        present = [r[j] is not None for r in flat]
+        empty = [] if kind & (VAL_LIST | VAL_SET) else b"" if kind == VAL_STR else 0
+        column = [empty if r[j] is None else r[j] for r in flat]
+        cols.append(_host_column(kind, column, len(flat), None if all(present) else present))
+    return cols, row_off, len(flat)
+
+
+def row_values_batch(rows, plan, ctx: Optional[Context] = None):
+    """The host path (dg_rvals_batch_host): `rows` is, per message, a list of
+    rows; a row is a tuple in column order, with None for an absent field
+    (values as values_batch takes them). `plan` is a RowValuePlan or a list of
+    (field_id, kind). Returns (arena uint8, off uint64[n + 1], status uint8[n],
+    cell_status uint8[n_rows * K]): message i's list is arena[off[i]:off[i + 1]]."""
+    wp = plan if isinstance(plan, RowValuePlan) else RowValuePlan([f[1] for f in plan], [f[0] for f in plan], "list", ctx)
+    with _unless_given(wp, plan):
+        if not rows:
+            return np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint8), np.zeros(0, np.uint8)
+        cols, row_off, n_rows = _rows_as_columns(wp, rows)
+        return _row_values_host(wp, cols, row_off, len(rows), n_rows)
+
+
+def set_rows_batch(msgs: Sequence[bytes], path, fields, rows, container="list", desc=None, root_type: int = STRUCT,
+                   ctx: Optional[Context] = None) -> List[EditManyResult]:
+    """SetMany of one list<struct> per message: `fields` is a list of (field_id,
+    kind), `rows` per message a list of rows (row_values_batch); the list is
+    encoded on the device and set as the child that `path`'s last step names,
+    below the node at the steps before it (set_many_batch's host entry with one
+    item of the plan's wire type). The statuses of row_values_batch are not
+    returned, as set_columns_batch returns none: a message flagged SIZE is set
+    as the empty list and a flagged cell as the empty value of its kind; call
+    row_values_batch where they matter."""
+    path = list(path)
+    if not path:
+        raise ValueError("the empty path names no item")
+    if len(rows) != len(msgs):
+        raise ValueError("%d row lists for %d messages" % (len(rows), len(msgs)))
+    with RowValuePlan([f[1] for f in fields], [f[0] for f in fields], container, ctx) as wp:
+        arena, off, _, _ = row_values_batch(rows, wp)
+        with EditManyPlan(path[:-1], [path[-1]], EDIT_SET, desc, ctx) as plan:
+            return _editm_batch(msgs, plan, None, [wp.wire_type], root_type, encoded=(arena, off))
+
+
+def build_row_lists_batch(fields, rows, container="list", ctx: Optional[Context] = None) -> List[bytes]:
+    """NewNodeList of structs for a batch: `fields` is a list of (field_id,
+    kind), `rows` per message a list of rows (row_values_batch); returns the
+    bare list values as bytes. The statuses are not returned: a flagged message
+    is the empty list, a flagged cell the empty value (row_values_batch gives
+    them)."""
+    with RowValuePlan([f[1] for f in fields], [f[0] for f in fields], container, ctx) as wp:
+        arena, off, _, _ = row_values_batch(rows, wp)
+        return _split(arena, off)

@@ -1307,6 +1307,102 @@ int dg_evals_batch_device(dg_ctx *ctx, const dg_evals *plan, const dg_eval_col *
 int dg_evals_batch_host(dg_ctx *ctx, const dg_evals *plan, const dg_eval_col *cols, uint64_t n, uint8_t *out, uint64_t cap,
                         uint64_t *out_off, uint8_t *status, uint64_t *need);
 
+/* ------------------------------------------------------------------------
+ * rvals: row column writes, the inverse of rows and a component beside vals
+ * and evals (neither takes struct elements): ragged row tensors encoded to
+ * list<struct> and set<struct> values (the reference's NewNodeList /
+ * NewNodeSet over []interface{} of map[FieldID]interface{},
+ * thrift/generic/node.go:154-187, over WriteAny, thrift/binary.go:1504-1528 and
+ * :1661). A plan holds the outer container's wire type, 15 (LIST) or 14 (SET),
+ * and K columns, 1 <= K <= DG_VALS_MAX_COLS, each with one of vals' 19 kinds
+ * (the six fixed-width scalars, STRING, DG_VAL_LIST | elem and DG_VAL_SET | elem
+ * over the six) and a field id; the field ids are required, the elements being
+ * structs. Lists of bare scalars stay with dg_vals_*, lists of strings with
+ * dg_evals_*. dg_rvals_create answers DG_E_ARG with a text naming it for any
+ * other kind ("column j: unknown kind N"), K, container or for no field ids.
+ *
+ * Inputs: d_row_off (u64, n + 1), the array dg_rows_batch_device writes:
+ * message i owns the rows [d_row_off[i], d_row_off[i + 1]) of the per-row
+ * arrays, which hold n_rows rows (a host value, as evals' n_ent). cols: K
+ * dg_val_col records indexed by row: d_val[n_rows], d_len[n_rows], d_src,
+ * d_elem_off[n_rows + 1], d_elems, d_present[n_rows] (optional), the shapes
+ * dg_rows_batch_device and dg_rows_list_device write, so their outputs plug in
+ * unchanged. n_rows * K < 2^32 (the scan's limit) and n < 2^32.
+ *
+ * What message i writes: one item, in the form dg_editm_batch_device takes as
+ * d_val / d_val_off for one item of wire type 15 or 14: 0C, the i32 big-endian
+ * count, then its rows in order. A row is every present column in column
+ * order, each as EncodeFieldBegin(wire type, id), 3 bytes, and the value as
+ * dg_vals writes it in struct mode, then 00 (STOP). A row with no column
+ * present is the STOP byte alone; an empty list is 5 bytes.
+ *
+ * Statuses, both arrays optional:
+ *   d_status (u8, n)  DG_EVAL_E_RANGE: d_row_off[i] > d_row_off[i + 1] or
+ *                     d_row_off[i + 1] > n_rows, tested first. DG_VAL_E_SIZE: a
+ *                     count above 2^31 - 1, or an item of 2^32 bytes or more.
+ *                     Either writes the message as the empty container
+ *                     (0C 00 00 00 00).
+ *   d_cell_status (u8, n_rows * K, row-major)  vals' DG_VAL_E_SIZE rule per
+ *                     cell, unchanged: the flagged cell is written as the empty
+ *                     value of its kind, the row and the message stay OK.
+ * The per-row arrays (values, lengths, element offsets, present) are read for
+ * every row below n_rows and for none at or beyond it. No payload byte and no
+ * element is read for a row that no OK message owns, for an absent cell or for
+ * a flagged cell. Row ranges may overlap or leave gaps, as evals' entry ranges:
+ * a row owned by two messages is written twice.
+ *
+ * Deviations from the reference:
+ *   1. Count 0 is legal (WriteAny refuses an empty []interface{}).
+ *   2. Fields go in column order (Go's map order is unspecified).
+ *   3. Nested structs, maps, strings inside inner lists and WriteAnyWithDesc
+ *      stay out.
+ *   4. The struct message around the list stays out: the item is inserted with
+ *      dg_editm (set_many), as evals' deviation 4 does.
+ */
+typedef struct dg_rvals dg_rvals;
+int dg_rvals_create(dg_ctx *ctx, const uint8_t *kinds, uint32_t K, const int16_t *field_ids, uint8_t container,
+                    dg_rvals **out);
+void dg_rvals_destroy(dg_rvals *p);
+uint32_t dg_rvals_count(const dg_rvals *p);
+/* the wire type of every message's item (dg_editm_batch_device's val_types[k]): 15 or 14; 0 for a NULL plan */
+uint8_t dg_rvals_wire_type(const dg_rvals *p);
+/* the bytes of d_work that suffice for any batch of n messages over n_rows
+ * rows: per cell its length and its position (12 bytes), per message its
+ * length, its count and its scanned count (16 bytes), and one set of tile sums.
+ * A plan of scalars whose columns all come without d_present (the fixed-stride
+ * route) uses the per-message part and the sums only, and the call takes a
+ * d_work of that size. 0 for a NULL plan, n >= 2^32 or n_rows * K >= 2^32. */
+uint64_t dg_rvals_work_bytes(const dg_rvals *p, uint64_t n, uint64_t n_rows);
+
+/* Device buffers, stream-ordered, async (stream NULL: the context's). cols: K
+ * records in HOST memory whose pointers are device pointers. The output is a
+ * message-major arena with one item per message: d_out_off (u64, n + 1 entries,
+ * 8-byte aligned), [0] = out_base, [n] the arena's end; d_out with cap + 16
+ * bytes allocated, nothing stored at an index >= cap and the 16 spare bytes
+ * untouched. d_out NULL stops after the offsets and statuses (sizing). n = 0
+ * returns DG_OK and launches nothing. d_work (8-byte aligned; short: DG_E_NOMEM)
+ * is the call's only storage: nothing is allocated, and calls on several
+ * streams need a d_work each. The passes: a cell-size pass, one lane per (row,
+ * column), and cols' scan of the lengths (neither on the fixed-stride route); a
+ * message pass, one lane per message, and the scans of the messages' lengths
+ * (into d_out_off) and row counts; a head pass, one lane per cell of every
+ * emitted row; and, for a plan with a STRING or container column, vals' body
+ * pass over the arena's bytes, in which whole waves store contiguous runs. Rows
+ * are placed by the scans and written row-parallel, so one message of 10 000
+ * rows costs what the same rows cost spread evenly. */
+int dg_rvals_batch_device(dg_ctx *ctx, const dg_rvals *plan, const dg_val_col *cols, const uint64_t *d_row_off, uint64_t n,
+                          uint64_t n_rows, uint64_t out_base, uint8_t *d_out, uint64_t cap, uint64_t *d_out_off,
+                          uint8_t *d_status, uint8_t *d_cell_status, void *d_work, uint64_t work_bytes, void *stream);
+/* Host buffers, synchronous (no spare bytes needed, no d_work): cols' pointers
+ * and row_off are host pointers, out_off (n + 1, never NULL) starts at 0,
+ * status (n) and cell_status (n_rows * K) may be NULL. The per-row arrays are
+ * uploaded whole, payloads and elements from the first to the last byte a live
+ * cell reads. *need = the arena's bytes. out NULL with cap 0 stops there
+ * (sizing); otherwise DG_E_NOMEM when cap < *need. */
+int dg_rvals_batch_host(dg_ctx *ctx, const dg_rvals *plan, const dg_val_col *cols, const uint64_t *row_off, uint64_t n,
+                        uint64_t n_rows, uint8_t *out, uint64_t cap, uint64_t *out_off, uint8_t *status, uint8_t *cell_status,
+                        uint64_t *need);
+
 /* Timing helper for benchmarks: launch the device batch `iters` times on the
  * context stream bracketed by HIP events; returns total milliseconds of GPU
  * time in *ms (events are recorded on the stream the kernels run on). */
