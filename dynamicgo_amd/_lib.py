@@ -33,7 +33,8 @@ EXPORTS = ["dg_last_error", "dg_build_info", "dg_ctx_create", "dg_ctx_destroy", 
            "dg_ents_create", "dg_ents_destroy", "dg_ents_count", "dg_ents_batch_device", "dg_ents_emit_device",
            "dg_ents_batch_host",
            "dg_rows_create", "dg_rows_destroy", "dg_rows_count", "dg_rows_batch_device", "dg_rows_list_device",
-           "dg_rows_batch_host",
+           "dg_rows_batch_host", "dg_rows_create_map", "dg_rows_key_kind", "dg_rows_map_batch_device",
+           "dg_rows_map_batch_host",
            "dg_vals_create", "dg_vals_destroy", "dg_vals_count", "dg_vals_wire_type", "dg_vals_batch_device",
            "dg_vals_batch_host",
            "dg_evals_create", "dg_evals_destroy", "dg_evals_count", "dg_evals_wire_type", "dg_evals_work_bytes",
@@ -161,6 +162,10 @@ def lib() -> C.CDLL:
         "dg_rows_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, u64]),
         "dg_rows_list_device": (i32, [vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
         "dg_rows_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, P64]),
+        "dg_rows_create_map": (i32, [vp, C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, u32, u32, C.POINTER(vp)]),
+        "dg_rows_key_kind": (u32, [vp]),
+        "dg_rows_map_batch_device": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, u64]),
+        "dg_rows_map_batch_host": (i32, [vp, vp, C.c_uint8, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u64, P64]),
         "dg_vals_create": (i32, [vp, C.c_char_p, u32, vp, C.POINTER(vp)]),
         "dg_vals_destroy": (None, [vp]),
         "dg_vals_count": (u32, [vp]),

@@ -490,6 +490,7 @@ static_assert(DG_ROWS_MAX_COLS == DG_TGET_MAX_PATHS, "a kind per sub-path");
 struct dg_rows : PlanRec {
     DevArr<uint8_t> d_sub;
     dg_path_hdr sub_hdr;
+    uint32_t key_kind = 0; /* 0: a list plan; DG_ROWS_KEY_*: a map plan (dg_rows_create_map) */
 };
 
 /* one batch of messages (device pointers) and where the lookup's records go */

@@ -1,6 +1,6 @@
 /* rows kernels (row columns, rows_device.h): the head, index and row cell
- * passes, three operations of the pair pass (walk_kern.h). The scan between
- * them is cols'. */
+ * passes, three operations of the pair pass (walk_kern.h), and the map plans'
+ * head and index passes, two more. The scan between them is cols'. */
 #include "rows_device.h"
 #include "walk_kern.h"
 
@@ -64,6 +64,33 @@ struct RowsCellOp : RowsOp {
     template <class FR>
     static __device__ __forceinline__ bool deep(const RWParams &A, uint64_t q, const FR &fr) { return pair(A, q, fr, true); }
 };
+
+/* The map plans' head and index passes: the same geometry over RWMapParams.
+ * Operations of their own, so the list kernels above are instantiated from
+ * exactly the code they were. */
+struct RowsMapOp : RowsOp {
+    using Params = RWMapParams;
+    static __device__ __forceinline__ uint64_t pairs(const RWMapParams &A) { return A.n; }
+};
+struct RowsMapHeadOp : RowsMapOp {
+    template <class FR>
+    static constexpr bool (*lane)(const RWMapParams &, uint64_t, const FR &) = &rw_map_head_msg<FR>;
+    template <class FR>
+    static __device__ __forceinline__ void deep(const RWMapParams &A, uint64_t i, const FR &fr)
+    {
+        if (rw_map_head_msg(A, i, fr)) rw_put_head(A, i, 0, 0, DG_TGET_E_READ, 0, 0, A.n_steps); /* unreachable: 1023 levels fit */
+    }
+};
+struct RowsMapIndexOp : RowsMapOp {
+    template <class FR>
+    static constexpr bool (*lane)(const RWMapParams &, uint64_t, const FR &) = &rw_map_index_msg<FR>;
+    template <class FR>
+    static constexpr bool (*deep)(const RWMapParams &, uint64_t, const FR &) = &rw_map_index_msg<FR>;
+};
+
+void launch_rows_map_head(hipStream_t s, const RWMapParams &A) { launch_walk<RowsMapHeadOp>(s, A, A.n); }
+
+void launch_rows_map_index(hipStream_t s, const RWMapParams &A) { launch_walk<RowsMapIndexOp>(s, A, A.n); }
 
 void launch_rows_head(hipStream_t s, const RWParams &A) { launch_walk<RowsHeadOp>(s, A, A.n); }
 

@@ -1155,6 +1155,8 @@ ROWS_MAX_COLS = 8  # DG_ROWS_MAX_COLS
 ROWS_HEAD_DTYPE = np.dtype([("first", "<u8"), ("count", "<u4"), ("status", "u1"), ("type", "u1"), ("elem_type", "u1"),
                             ("step", "u1")])  # dg_rows_head
 ROW_ENT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("msg", "<u4")])  # dg_row_ent
+ROWS_KEY_STR, ROWS_KEY_INT = 1, 2  # DG_ROWS_KEY_*
+_ROWS_KEYS = {None: 0, "str": ROWS_KEY_STR, "int": ROWS_KEY_INT}
 
 
 class RowPlan(_Handle):
@@ -1163,25 +1165,35 @@ class RowPlan(_Handle):
     element of the list or set the parent path ends at, the kind is col_kind's.
     PathFieldName steps of the parent are resolved through `desc`, those of a
     sub-path through the descriptor of the list's elements; a name step
-    without a descriptor raises (dg_rows)."""
+    without a descriptor raises (dg_rows). keys = "str" or "int" makes a map
+    plan: the parent path ends at a map<string, V> or a map of integer keys,
+    a row is an entry, the sub-paths are looked up in its value (names
+    through the descriptor of the map's values) and every row has its key."""
     _destroy = "dg_rows_destroy"
 
-    def __init__(self, parent, columns, desc=None, ctx: Optional[Context] = None):
+    def __init__(self, parent, columns, desc=None, ctx: Optional[Context] = None, keys=None):
+        if keys not in _ROWS_KEYS:
+            raise ValueError("unknown key kind %r (\"str\", \"int\" or None)" % (keys,))
         self.ctx = ctx or default_context()
+        self.keys, self.key_kind = keys, _ROWS_KEYS[keys]
         self.kinds = [col_kind(k) for _, k in columns]
         steps, at = _resolve_to(list(parent), desc)
         self.parent_blob = compile_paths([steps])
         self.blob = compile_paths([list(p) for p, _ in columns], at.elem if at is not None else None)
         h = C.c_void_p()
-        _lib.check(_lib.lib().dg_rows_create(self.ctx.h, self.parent_blob, len(self.parent_blob), self.blob, len(self.blob),
-                                             bytes(self.kinds), len(self.kinds), C.byref(h)))
+        args = (self.ctx.h, self.parent_blob, len(self.parent_blob), self.blob, len(self.blob), bytes(self.kinds),
+                len(self.kinds))
+        if self.key_kind:
+            _lib.check(_lib.lib().dg_rows_create_map(*args, self.key_kind, C.byref(h)))
+        else:
+            _lib.check(_lib.lib().dg_rows_create(*args, C.byref(h)))
         self.h = h
         self.count = int(_lib.lib().dg_rows_count(h))
         self.lists = [k for k, kind in enumerate(self.kinds) if kind & COL_LIST]
 
 
 def rows_device(plan: RowPlan, thrift, in_off, n: int, head, row_off, index=None, val=None, cell=None, lens=None,
-                row_cap: int = 0, root_type: int = STRUCT, stream=None, max_len: int = 0):
+                row_cap: int = 0, root_type: int = STRUCT, stream=None, max_len: int = 0, keys=None, key_lens=None):
     """Device-resident batch (dg_rows_batch_device) over torch tensors or raw
     device pointers: thrift uint8[>= in_off[n] + 16]; in_off int64[n + 1]; head
     n 16-byte heads (e.g. int32 of shape (n, 4)); row_off int64[n + 1]
@@ -1192,8 +1204,17 @@ def rows_device(plan: RowPlan, thrift, in_off, n: int, head, row_off, index=None
     row_off; with index given, the index too). No row at an
     index >= row_cap is stored. Asynchronous on `stream` (a torch stream, a raw
     stream handle, or None for torch's current stream when `thrift` is a
-    tensor)."""
+    tensor). A map plan goes to dg_rows_map_batch_device: keys int64[row_cap]
+    and key_lens int32[row_cap] (each may be None) receive every indexed row's
+    key: an int key's value and width, a string key's arena offset and length."""
     s = _stream_handle(stream, thrift)
+    if plan.key_kind:
+        _lib.check(_lib.lib().dg_rows_map_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n,
+                                                       _ptr(head), _ptr(row_off), _ptr(index), _ptr(keys), _ptr(key_lens),
+                                                       _ptr(val), _ptr(cell), _ptr(lens), row_cap, s, max_len))
+        return
+    if keys is not None or key_lens is not None:
+        raise ValueError("keys for a list plan")
     _lib.check(_lib.lib().dg_rows_batch_device(plan.ctx.h, plan.h, root_type, _ptr(thrift), _ptr(in_off), n, _ptr(head),
                                                _ptr(row_off), _ptr(index), _ptr(val), _ptr(cell), _ptr(lens), row_cap, s,
                                                max_len))
@@ -1216,9 +1237,19 @@ def rows_records(msgs: Sequence[bytes], plan: RowPlan, root_type: int = STRUCT, 
     uint64[n + 1], index ROW_ENT_DTYPE[R], val uint64[P, R], cell
     COL_CELL_DTYPE[P, R], lens uint32[P, R], arena); offsets point into `arena`,
     the messages back to back. count_only stops after the heads (R = 0 rows
-    come back): head["count"] is batched Node.Len."""
+    come back): head["count"] is batched Node.Len. A map plan goes through
+    dg_rows_map_batch_host and gets two more items behind the seven: key
+    uint64[R] and key_len uint32[R]."""
     n, P = len(msgs), plan.count
     lib = _lib.lib()
+    if plan.key_kind:
+        def host(thrift, in_off, n, head, row_off, index, val, cell, lens, cap, need, key=None, key_len=None):
+            return lib.dg_rows_map_batch_host(plan.ctx.h, plan.h, root_type, thrift, in_off, n, head, row_off, index, key,
+                                              key_len, val, cell, lens, cap, need)
+    else:
+        def host(thrift, in_off, n, head, row_off, index, val, cell, lens, cap, need):
+            return lib.dg_rows_batch_host(plan.ctx.h, plan.h, root_type, thrift, in_off, n, head, row_off, index, val, cell,
+                                          lens, cap, need)
     head = np.zeros(n, dtype=ROWS_HEAD_DTYPE)
     row_off = np.zeros(n + 1, dtype=np.uint64)
     need = C.c_uint64(0)
@@ -1227,20 +1258,23 @@ def rows_records(msgs: Sequence[bytes], plan: RowPlan, root_type: int = STRUCT, 
         return (np.zeros(R, dtype=ROW_ENT_DTYPE), np.zeros((P, R), dtype=np.uint64), np.zeros((P, R), dtype=COL_CELL_DTYPE),
                 np.zeros((P, R), dtype=np.uint32))
 
+    def keys(R):
+        return (np.zeros(R, dtype=np.uint64), np.zeros(R, dtype=np.uint32)) if plan.key_kind else ()
+
     if n == 0:
-        _lib.check(lib.dg_rows_batch_host(plan.ctx.h, plan.h, root_type, None, None, 0, None, row_off.ctypes.data, None, None,
-                                          None, None, 0, C.byref(need)))
-        return (head, row_off) + outs(0) + (np.zeros(16, dtype=np.uint8),)
+        _lib.check(host(None, None, 0, None, row_off.ctypes.data, None, None, None, None, 0, C.byref(need)))
+        return (head, row_off) + outs(0) + (np.zeros(16, dtype=np.uint8),) + keys(0)
     arena, in_off = _arena(msgs)
-    _lib.check(lib.dg_rows_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
-                                      head.ctypes.data, row_off.ctypes.data, None, None, None, None, 0, C.byref(need)))
+    _lib.check(host(arena.ctypes.data, in_off.ctypes.data, n, head.ctypes.data, row_off.ctypes.data, None, None, None, None, 0,
+                    C.byref(need)))
     R = 0 if count_only else int(need.value)
     index, val, cell, lens = outs(R)
+    kv = keys(R)
     if R:
-        _lib.check(lib.dg_rows_batch_host(plan.ctx.h, plan.h, root_type, arena.ctypes.data, in_off.ctypes.data, n,
-                                          head.ctypes.data, row_off.ctypes.data, index.ctypes.data, val.ctypes.data,
-                                          cell.ctypes.data, lens.ctypes.data, R, C.byref(need)))
-    return head, row_off, index, val, cell, lens, arena
+        _lib.check(host(arena.ctypes.data, in_off.ctypes.data, n, head.ctypes.data, row_off.ctypes.data, index.ctypes.data,
+                        val.ctypes.data, cell.ctypes.data, lens.ctypes.data, R, C.byref(need),
+                        *(a.ctypes.data for a in kv)))
+    return (head, row_off, index, val, cell, lens, arena) + kv
 
 
 def _row_list_elems(plan: RowPlan, k: int, arena, val_k, cell_k, len_k):
@@ -1270,8 +1304,12 @@ class Rows:
     .offsets (int64[n + 1]: message i owns rows offsets[i]:offsets[i + 1]),
     .index (ROW_ENT_DTYPE[R]: every row's element span in the arena and its
     message) and .columns, one Column per row column over the R rows (a list
-    kind's .offsets index its elements by row)."""
-    __slots__ = ("head", "status", "offsets", "index", "columns")
+    kind's .offsets index its elements by row). Under a map plan a row is an
+    entry of the map, .index its value's span, and .keys holds the rows' keys:
+    int64[R] for int keys, a list of R bytes for string keys, with
+    .key_lengths (uint32[R]) the string keys' lengths or the int keys' widths
+    in bytes; both are None under a list plan."""
+    __slots__ = ("head", "status", "offsets", "index", "columns", "keys", "key_lengths")
 
     def error(self, i: int):
         return COL_ERROR_NAMES.get(int(self.status[i]), "ErrRead")
@@ -1281,15 +1319,21 @@ class Rows:
 
 
 def rows_batch(msgs: Sequence[bytes], parent, columns=None, desc=None, root_type: int = STRUCT,
-               ctx: Optional[Context] = None) -> Rows:
+               ctx: Optional[Context] = None, keys=None) -> Rows:
     """For every message the list or set at `parent` and, for every element of
     it, GetByPath(sub_path) and a cast: `columns` is a list of (sub_path, kind);
-    `parent` may be a RowPlan instead (then `columns` is not given)."""
-    plan = parent if isinstance(parent, RowPlan) else RowPlan(parent, columns, desc, ctx)
+    `parent` may be a RowPlan instead (then `columns` is not given). keys =
+    "str" or "int": `parent` ends at a map, the rows are its entries."""
+    plan = parent if isinstance(parent, RowPlan) else RowPlan(parent, columns, desc, ctx, keys)
     with _unless_given(plan, parent):
-        head, row_off, index, val, cell, lens, arena = rows_records(msgs, plan, root_type)
+        head, row_off, index, val, cell, lens, arena, *kv = rows_records(msgs, plan, root_type)
         out = Rows()
         out.head, out.status, out.offsets, out.index = head, head["status"], row_off.astype(np.int64), index
+        out.keys = out.key_lengths = None
+        if plan.key_kind:
+            out.key_lengths = kv[1]
+            out.keys = kv[0].view(np.int64) if plan.key_kind == ROWS_KEY_INT else \
+                [arena[int(o):int(o) + int(ln)].tobytes() for o, ln in zip(kv[0], kv[1])]
         out.columns = []
         for k, kind in enumerate(plan.kinds):
             c = Column()

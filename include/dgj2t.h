@@ -1040,6 +1040,72 @@ int dg_rows_batch_host(dg_ctx *ctx, const dg_rows *rows, uint8_t root_type, cons
                        const uint64_t *in_off, uint64_t n, dg_rows_head *head, uint64_t *row_off, dg_row_ent *index,
                        uint64_t *val, dg_col_cell *cell, uint32_t *len, uint64_t row_cap, uint64_t *need);
 
+/* Map plans: the entries of a map<K, V> as rows, with their keys ("the price of
+ * every SKU in prices: map<string, Item>"): what the reference's loop
+ *     v.GetByPath(parent...).Children(&kids, false, opts)
+ *     for each kid: kid.Path is the key; kid.Node.GetByPath(sub_k...) and the
+ *                   cast of column k is the cell
+ * gives over a MAP node. A map plan is a rows plan with a key kind
+ * (DG_ROWS_KEY_STR or DG_ROWS_KEY_INT); a list plan behaves as above, and a
+ * MAP parent under a list plan stays DG_COL_E_UNSUPPORTED.
+ *
+ *   head (message i)   in this order: the lookup's status and step on failure
+ *                      (under a non-empty path the node's skip comes first,
+ *                      DG_TGET_E_READ with step = the path's length on failure,
+ *                      and the depth budget starts one lower); a node that is
+ *                      not MAP (LIST and SET too) is DG_COL_E_UNSUPPORTED with
+ *                      type = the wire type found; the header is read as
+ *                      ReadMapBegin reads it (a key or value type that is not
+ *                      Valid(), or a negative size, is DG_TGET_E_READ); a key
+ *                      type the plan's key kind does not take (STR: STRING
+ *                      only; INT: I08 / I16 / I32 / I64 only) is
+ *                      DG_COL_E_UNSUPPORTED with type = MAP and elem_type = the
+ *                      key type found, at any size, 0 included; an entry whose
+ *                      key or value fails to skip makes the message
+ *                      DG_TGET_E_READ with no rows. OK: count = Node.Len(),
+ *                      type = MAP, elem_type = the VALUE type (the root type of
+ *                      every row's lookup), first = the arena offset of entry
+ *                      0's key, the byte after the 6-byte header.
+ *                      The key-type rule deviates: the reference's Children
+ *                      yields PathBinKey for other key types; the restriction
+ *                      is StrMap's / IntMap's, as in dg_ents_*.
+ *   rows               in wire order, duplicate keys kept. The index entry
+ *                      (dg_row_ent) is the VALUE's span and the message.
+ *   key (row g)        d_key[g]: an int key is the value as ReadInt and
+ *                      dg_kid_rec.key give it (I08 unsigned: 0xFF is 255; I16,
+ *                      I32, I64 sign-extended); a string key is the arena
+ *                      offset of its payload. d_key_len[g]: a string key's
+ *                      payload length; an int key's width in bytes (1, 2, 4 or
+ *                      8), which tells the wire type. No key of a row >=
+ *                      row_cap is stored.
+ *   cell (g, k)        exactly the list plan's, on the value's own bytes; the
+ *                      lookup's end is the value's end.
+ */
+/* As dg_rows_create with its limits and texts (one parent path, 1 to
+ * DG_ROWS_MAX_COLS sub-paths, cols' kinds); an unknown key_kind is DG_E_ARG
+ * with a text. */
+int dg_rows_create_map(dg_ctx *ctx, const void *parent_blob, size_t parent_len, const void *sub_blob, size_t sub_len,
+                       const uint8_t *kinds, uint32_t n_kinds, uint32_t key_kind, dg_rows **out);
+/* DG_ROWS_KEY_STR or DG_ROWS_KEY_INT; 0 for a list plan (and for NULL) */
+uint32_t dg_rows_key_kind(const dg_rows *p);
+/* dg_rows_batch_device / dg_rows_batch_host for a map plan: their arguments,
+ * sizing call, index-only call, row_cap rules, row_cap * P < 2^32 rule and
+ * n = 0, plus d_key (u64, row_cap entries, 8-byte aligned) and d_key_len (u32,
+ * row_cap entries), each of which may be NULL: not wanted. The keys are
+ * written by the index pass, for exactly the rows whose index entries are
+ * (into d_index or the component's scratch). The host entry's string-key
+ * offsets are relative to `thrift`. A list plan here, and a map plan at
+ * dg_rows_batch_device / dg_rows_batch_host, is DG_E_ARG with a text;
+ * dg_rows_list_device takes both, since it only reads cells. */
+int dg_rows_map_batch_device(dg_ctx *ctx, const dg_rows *rows, uint8_t root_type, const uint8_t *d_thrift,
+                             const uint64_t *d_in_off, uint64_t n, dg_rows_head *d_head, uint64_t *d_row_off,
+                             dg_row_ent *d_index, uint64_t *d_key, uint32_t *d_key_len, uint64_t *d_val,
+                             dg_col_cell *d_cell, uint32_t *d_len, uint64_t row_cap, void *stream, uint64_t max_len);
+int dg_rows_map_batch_host(dg_ctx *ctx, const dg_rows *rows, uint8_t root_type, const uint8_t *thrift,
+                           const uint64_t *in_off, uint64_t n, dg_rows_head *head, uint64_t *row_off, dg_row_ent *index,
+                           uint64_t *key, uint32_t *key_len, uint64_t *val, dg_col_cell *cell, uint32_t *len,
+                           uint64_t row_cap, uint64_t *need);
+
 /* ------------------------------------------------------------------------
  * ents: entry columns, the containers cols leaves out: GetByPath followed by
  * Node.List with String per element, Node.StrMap or Node.IntMap

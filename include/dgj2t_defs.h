@@ -327,6 +327,14 @@ typedef struct dg_row_ent {
     uint32_t len; /* the element's byte length */
     uint32_t msg; /* the message the row belongs to */
 } dg_row_ent; /* 16 bytes */
+/* The key kind of a map plan (dg_rows_create_map): the rows are the entries of
+ * a map, the index entry is the VALUE's span, and each row has a key beside it.
+ * Under a map plan an OK head's type is MAP, elem_type the value type and first
+ * the arena offset of entry 0's key (the byte after the 6-byte header); a key
+ * type the kind does not take is DG_COL_E_UNSUPPORTED with type = MAP and
+ * elem_type = the key type found. */
+#define DG_ROWS_KEY_STR 1u /* STRING keys: the payload's arena offset and length */
+#define DG_ROWS_KEY_INT 2u /* I08 / I16 / I32 / I64 keys: the value as ReadInt gives it, and the width in bytes */
 
 /* ents (entry columns, include/dgj2t.h dg_ents_*): Node.List with String per
  * element, Node.StrMap and Node.IntMap as ragged columns. A kind is
